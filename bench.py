@@ -10,10 +10,19 @@ MT19937 streams included) and the fused observation of drone 0 (K=1, the
 window train_jax.py:55-56 feeds the DQN).  Actions are synthetic uniform
 {0..4}, generated before the timed region and resident in HBM.
 
-Launch:  python bench.py [--gpus 1] [--steps 500] [--warmup 50]
+Launch:  python bench.py [--gpus 1] [--steps 1000] [--warmup 50]
          python bench.py --gpus N          (starts its own N ranks, below)
          python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 Prints one JSON line on rank 0.
+
+A plain run does what the headline needs and nothing else: set-up, the
+pre-roll and warm-up, the `--steps` timed steps, the result line.  `--full`
+adds every other measurement to the line (the rocprofv3 traffic passes, the
+other observation store mode, strong scaling, the copy-peak probe, resets, the
+DQN consumer, drl_rollout, the train loops, the C5 north-star sub-record and
+the CPU baseline); the flags that trim or size those legs act under `--full`
+only.  `--dump-outputs DIR` writes what the last timed step returned to its
+caller (rewards, dones, observation) as DIR/<name>.npy.
 
 `--gpus N > 1` without a torch.distributed.run environment (no WORLD_SIZE):
 this process becomes a launcher.  Before touching the GPU it runs
@@ -1065,6 +1074,48 @@ class StepRunner:
                                    "step count"}}
 
 
+# the pre-generated action sets of one step loop: one per step up to this many (8.6 GB at C3), cycled beyond
+MAX_ACTION_SETS = 4096
+
+
+def action_sets(steps: int) -> int:
+    return max(1, min(steps, MAX_ACTION_SETS))
+
+
+# --dump-outputs: float32 bytes per array (a seeded sample of the rows beyond that); 8 + 8 + 44 MB <= 64 MB in all
+DUMP_BUDGET = {"rewards": 8 << 20, "dones": 8 << 20, "obs": 44 << 20}
+DUMP_SEED = 20240
+
+
+def dump_rows(n_rows: int, row_bytes: int, budget: int):
+    """The rows of an [n_rows, ...] array that --dump-outputs keeps: all of
+    them when they fit `budget` bytes, else a sorted sample without
+    replacement drawn from a fixed seed (the same rows in every run)."""
+    import numpy as np
+    keep = max(1, budget // row_bytes)
+    if n_rows <= keep:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n_rows, size=keep, replace=False))
+
+
+def dump_outputs(path: str, rewards, dones, obs):
+    """--dump-outputs: what the last timed step returned to its caller, the
+    step's own output buffers read back after the timed region: rewards
+    [E, N], dones [E, N] (0/1) and the observation [E, K, W, W, 6] (None at
+    K = 0), each as float32 in `path`/<name>.npy, env rows sampled by
+    dump_rows where an array exceeds its share of the 64 MB."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    for name, t in (("rewards", rewards), ("dones", dones), ("obs", obs)):
+        if t is None:
+            continue
+        rows = dump_rows(t.shape[0], t[0].numel() * 4, DUMP_BUDGET[name])
+        if rows is not None:
+            t = t.index_select(0, torch.from_numpy(rows).to(t.device))
+        np.save(os.path.join(path, name + ".npy"), t.to(torch.float32).cpu().numpy())
+
+
 def measure_copy_peak(dev, nbytes: int = 2 << 30, reps: int = 8):
     """the measured copy-kernel rate beside the 8 TB/s spec
     (MI355X_MICROARCH.md: 6.29 TB/s for a float4 copy).  drl_hbm_probe is that
@@ -1201,6 +1252,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=50)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline (traffic passes, the other store mode, "
+                         "strong scaling, copy peak, resets, DQN consumer, rollout, train loops, C5, CPU baseline); "
+                         "the flags below that trim or size those legs act with --full only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one returned (rewards, dones, observation) as "
+                         "DIR/<name>.npy (float32, at most 64 MB: a fixed seeded sample of the rows of a larger array)")
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     ap.add_argument("--envs", type=int, default=0, help="override envs per GPU")
     ap.add_argument("--c5-envs", type=int, default=CONFIGS["c5"][2],
@@ -1247,10 +1305,10 @@ def main():
     if needs_launch(args):  # N ranks as a child job, before this process touches the GPU
         sys.exit(launch_ranks(sys.argv[1:], args.gpus))
 
-    north = args.c5_envs > 0 and args.config != "c5"
+    north = args.full and args.c5_envs > 0 and args.config != "c5"
     names = [args.config] + (["c5"] if north else [])
     traffic_run = None
-    if (not args.no_pmc_traffic and int(os.environ.get("RANK", "0")) == 0
+    if (args.full and not args.no_pmc_traffic and int(os.environ.get("RANK", "0")) == 0
             and os.environ.get("DRL_BENCH_PMC", "1") != "0"):
         traffic_run = measure_traffic(args, names)  # child processes, before this one touches the GPU
 
@@ -1269,9 +1327,11 @@ def main():
 
     # ---- the headline: setup rolls one refill cycle (steady-state rings),
     # then W warm-up and K timed steps
-    runner = StepRunner(env, K, args.warmup + args.steps + 2 * env.refill_every, args.obs_stream)
+    runner = StepRunner(env, K, action_sets(args.warmup + args.steps + 2 * env.refill_every), args.obs_stream)
     main_res = runner.run(args.steps, args.warmup, world, pre=PRE_ROLL_CYCLES * env.refill_every)
     actions, rewards, dones, obs, stream = runner.actions, runner.rewards, runner.dones, runner.obs, runner.stream
+    if args.dump_outputs and rank == 0:  # before any other leg reuses the step's output buffers
+        dump_outputs(args.dump_outputs, rewards, dones, obs if K > 0 else None)
 
     def traffic_of(name):
         if traffic_run is not None and name in traffic_run:
@@ -1284,7 +1344,7 @@ def main():
 
     # ---- the other observation store mode, same steps
     other = None
-    if args.cached_steps > 0 and K > 0:
+    if args.full and args.cached_steps > 0 and K > 0:
         runner.obs_stream = not args.obs_stream
         nc = min(args.cached_steps, args.steps)
         o = runner.run(nc, min(args.warmup, 20), world)
@@ -1299,7 +1359,7 @@ def main():
     # ---- strong scaling (BASELINE.json's metric as written: num_envs = 65536
     # over the job): the same config, strong_envs / world envs per rank
     strong = None
-    if args.strong_envs > 0:
+    if args.full and args.strong_envs > 0:
         if world == 1:
             strong = {"value": main_res["value"], "num_envs_total": E, "n_gpus": 1, "scaling": "strong",
                       "note": "one rank: the headline itself" + ("" if E == args.strong_envs else
@@ -1307,7 +1367,8 @@ def main():
         else:
             Es = strong_split(args.strong_envs, world)
             env_s, _, _, _, _ = make_env(args.config, Es, rank, dev)
-            run_s = StepRunner(env_s, K, args.warmup + args.steps + 2 * env_s.refill_every, args.obs_stream)
+            run_s = StepRunner(env_s, K, action_sets(args.warmup + args.steps + 2 * env_s.refill_every),
+                               args.obs_stream)
             rs = run_s.run(args.steps, args.warmup, world, pre=PRE_ROLL_CYCLES * env_s.refill_every)
             strong = {"value": rs["value"], "unit": "env-steps/s", "scaling": "strong", "n_gpus": world,
                       "num_envs_total": args.strong_envs, "num_envs_per_gpu": Es, "steps": args.steps,
@@ -1317,11 +1378,11 @@ def main():
             del run_s, env_s
             torch.cuda.synchronize()
 
-    copy_peak = measure_copy_peak(dev)
+    copy_peak = measure_copy_peak(dev) if args.full else None
 
     # resets (train_jax.py:101-113 resets every 100 steps in C5): timed separately
     resets_per_s = None
-    if not args.no_reset_bench:
+    if args.full and not args.no_reset_bench:
         env.reset(seed=None)
         torch.cuda.synchronize()
         r0, r1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -1334,12 +1395,12 @@ def main():
         resets_per_s = E * world * nres / (r0.elapsed_time(r1) / 1e3)
 
     dqn = None
-    if K >= 1 and not args.no_dqn:
+    if args.full and K >= 1 and not args.no_dqn:
         dqn = dqn_consumer_bench(env, actions, rewards, dones, obs, args.warmup, min(args.steps, 200), stream,
                                  args.loop_precision, loop_input(args, env))
 
     roll = None
-    if args.rollout_chunk > 0:
+    if args.full and args.rollout_chunk > 0:
         env.reset(seed=0)
         roll = rollout_bench(env, actions, K, args.warmup, args.steps, args.rollout_chunk, R, Wb, world)
         if K > 0:  # jax run_steps exactly (no observation): rewards/dones of every step only
@@ -1349,7 +1410,7 @@ def main():
             roll["no_obs"] = {k: r0[k] for k in ("value", "ms_per_step")}
 
     loop = None
-    if args.loop_segments > 0 and not args.no_dqn and K >= 1:
+    if args.full and args.loop_segments > 0 and not args.no_dqn and K >= 1:
         loop = train_loop_bench(env, args.loop_segments, parallel=args.parallel_loop, fused=not args.unfused_act,
                                 precision=args.loop_precision, input=loop_input(args, env))
         loop["env_steps_per_s"] = min_over_ranks(loop["env_steps_per_s"], world) * world
@@ -1397,7 +1458,7 @@ def main():
         del env5
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(G, N, K, args.cpu_seconds)
 
     if rank == 0:

@@ -58,7 +58,7 @@ def test_cpu_baseline_record():
 def test_cli_help_lists_contract_flags():
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--help"], capture_output=True,
                          text=True, timeout=120, check=True).stdout
-    for flag in ("--gpus", "--steps", "--warmup", "--config", "--cached-steps", "--no-pmc-traffic", "--c5-envs",
+    for flag in ("--gpus", "--steps", "--warmup", "--full", "--dump-outputs", "--config", "--cached-steps", "--no-pmc-traffic", "--c5-envs",
                  "--loop-precision"):
         assert flag in out
 
@@ -267,3 +267,31 @@ def test_cpu_baseline_quotes_reference_torch_impl():
         assert r["value"] > 0 and r["step_only_value"] > r["value"] and r["cores"] == 1
         assert "NOT the GPU box" in r["hardware"]
     assert bench.reference_torch_impl(12, 3) is None
+
+
+def test_dump_rows_fixed_sample_within_budget():
+    """--dump-outputs keeps every row of an array that fits its budget, else a
+    fixed sorted sample of distinct rows; at every config's size the three
+    arrays stay within 64 MB as float32."""
+    assert bench.dump_rows(1000, 32, 1000 * 32) is None
+    rows = bench.dump_rows(1000, 32, 999 * 32)
+    assert len(rows) == 999 and len(set(rows.tolist())) == 999 and (rows[1:] > rows[:-1]).all()
+    assert 0 <= rows[0] and rows[-1] < 1000
+    assert (rows == bench.dump_rows(1000, 32, 999 * 32 + 31)).all()  # no draw from the clock
+    assert len(bench.dump_rows(10, 64, 1)) == 1
+    assert sum(bench.DUMP_BUDGET.values()) <= 64 << 20
+    for G, N, E, K in bench.CONFIGS.values():
+        total = 0
+        for name, row in (("rewards", N * 4), ("dones", N * 4), ("obs", K * 7 * 7 * 6 * 4)):
+            r = bench.dump_rows(E, row, bench.DUMP_BUDGET[name])
+            total += (E if r is None else len(r)) * row
+        assert total <= 64 << 20
+
+
+def test_action_sets_are_bounded():
+    """One pre-generated action set per step up to MAX_ACTION_SETS, cycled beyond:
+    a long --steps run does not grow the resident actions without limit."""
+    assert bench.action_sets(20 + 5 + 64) == 89 and bench.action_sets(0) == 1
+    assert bench.action_sets(10 ** 6) == bench.MAX_ACTION_SETS
+    G, N, E, K = bench.CONFIGS["c3"]
+    assert bench.MAX_ACTION_SETS * E * N * 4 <= 16 << 30

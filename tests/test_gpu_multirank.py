@@ -114,8 +114,8 @@ def test_bench_two_ranks_gloo_whole_job_json():
     port = _free_port()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(REPO, "bench.py"),
-           "--gpus", "2", "--steps", "20", "--warmup", "5", "--envs", "4096", "--no-cpu-baseline", "--no-dqn",
-           "--no-reset-bench", "--rollout-chunk", "0", "--loop-segments", "0", "--cached-steps", "10",
+           "--gpus", "2", "--full", "--steps", "20", "--warmup", "5", "--envs", "4096", "--no-cpu-baseline",
+           "--no-dqn", "--no-reset-bench", "--rollout-chunk", "0", "--loop-segments", "0", "--cached-steps", "10",
            "--c5-envs", "1024", "--strong-envs", "4096"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=REPO)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -139,15 +139,15 @@ def test_bench_two_ranks_gloo_whole_job_json():
 
 
 def test_bench_gpus2_launches_its_own_ranks():
-    """a plain `bench.py --gpus 2` (no torchrun) starts
+    """a `bench.py --gpus 2` without torchrun (here with --full, for the C5 sub-record) starts
     its own 2 ranks (here gloo, both on the one GPU) and relays rank 0's one
     whole-job line: n_gpus 2, 2x the envs, and the north-star C5 sub-record
     at 131,072 envs per rank (262,144 over the job)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(DRL_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", DRL_BENCH_PMC="0")
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5",
-           "--envs", "4096", "--no-cpu-baseline", "--no-dqn", "--no-reset-bench", "--rollout-chunk", "0",
-           "--loop-segments", "0", "--cached-steps", "0"]
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--full", "--steps", "20",
+           "--warmup", "5", "--envs", "4096", "--no-cpu-baseline", "--no-dqn", "--no-reset-bench",
+           "--rollout-chunk", "0", "--loop-segments", "0", "--cached-steps", "0"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=REPO)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

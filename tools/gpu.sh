@@ -27,6 +27,8 @@ cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 TAG=${TAG:-}
+# the bench and configs tasks record every leg of the benchmark, not the headline alone
+BENCH_ARGS="--full ${BENCH_ARGS:-}"
 
 step() {  # step NAME SECONDS LOG CMD...: run one GPU step, stop the script on a crash / limit
   local name=$1 secs=$2 log=$3; shift 3

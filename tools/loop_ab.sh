@@ -4,7 +4,7 @@
 set -u
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
-A="--steps 20 --warmup 5 --no-cpu-baseline --no-reset-bench --rollout-chunk 0 --no-pmc-traffic --cached-steps 0 --c5-envs 0"
+A="--full --steps 20 --warmup 5 --no-cpu-baseline --no-reset-bench --rollout-chunk 0 --no-pmc-traffic --cached-steps 0 --c5-envs 0"
 for c in ${LCFGS:-c3 c5}; do
   for m in serial parallel; do
     P=""; [ $m = parallel ] && P="--parallel-loop"
