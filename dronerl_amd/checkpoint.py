@@ -208,12 +208,13 @@ def save_dense(path: str, weights, biases, obs_shape, format: str = "torch", con
 
 def to_qnet(ck: Checkpoint, device=None):
     """A dense checkpoint on the MFMA consumer (dronerl_amd.dqn.QNetwork).
-    Needs hidden widths that are multiples of 32 in [32, 128] (1-3 layers)."""
+    Needs hidden widths that are multiples of 8 in [8, 128] (1-3 layers): the
+    reference's default (16, 16) net among them."""
     from .dqn import QNetwork
     if ck.network_type != "dense":
         raise ValueError("only dense networks run on the MFMA consumer")
-    if not ck.dense_layers or len(ck.dense_layers) > 3 or any(w % 32 or not 32 <= w <= 128 for w in ck.dense_layers):
-        raise ValueError(f"hidden widths {ck.dense_layers} unsupported by drl_qnet (multiples of 32 in [32, 128])")
+    if not ck.dense_layers or len(ck.dense_layers) > 3 or any(w % 8 or not 8 <= w <= 128 for w in ck.dense_layers):
+        raise ValueError(f"hidden widths {ck.dense_layers} unsupported by drl_qnet (multiples of 8 in [8, 128])")
     n = len(ck.dense_layers) + 1
     net = QNetwork(int(np.prod(ck.obs_shape)), ck.dense_layers, int(ck.action_shape[0]), device=device)
     ws = [torch.from_numpy(np.array(ck.tensors[f"network.dense_{i + 1}.weight"])) for i in range(n)]

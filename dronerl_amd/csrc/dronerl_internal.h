@@ -247,9 +247,9 @@ struct ResetArgs {
 constexpr int QN_MAX_LAYERS = 4;
 struct QnetLayout {
     int n_layers;
-    int nt[QN_MAX_LAYERS];        // 16-row output tiles
-    int kt[QN_MAX_LAYERS];        // 32-wide K slices
-    int in[QN_MAX_LAYERS], out[QN_MAX_LAYERS];
+    int nt[QN_MAX_LAYERS];        // 16-row output tiles (a hidden layer: of its width rounded up to 32, so even)
+    int kt[QN_MAX_LAYERS];        // 32-wide K slices (layers >= 1: ceil(in / 32) = nt[l - 1] / 2)
+    int in[QN_MAX_LAYERS], out[QN_MAX_LAYERS];  // the logical sizes: rows >= out and k >= in of a fragment are zero pads
     int frag_off[QN_MAX_LAYERS];  // uint4 offset of the layer's fragments
     int bias_off[QN_MAX_LAYERS];  // float offset of the layer's biases (padded to 16 * nt)
     int frag_total;               // uint4s of fragments

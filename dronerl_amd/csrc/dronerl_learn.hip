@@ -153,8 +153,9 @@ __device__ __forceinline__ void dq_stage(int n, Src src, Dst dst) {
     }
 }
 
-// Layer l's weights of one net -> LDS, rows padded to in + 4 floats (in is a
-// multiple of 32: consecutive rows of a micro-tile start 4 banks apart).
+// Layer l's weights of one net -> LDS, rows padded to in + 4 floats (in a
+// multiple of 32: consecutive rows of a micro-tile start 4 banks apart; a
+// width that is only a multiple of 8 keeps the layout, not the bank pattern).
 __device__ __forceinline__ void dq_stage_w(const LearnArgs& a, const float* P, int l, float* Ws) {
     const int li = a.in[l], lo = a.out[l], ls = li + 4;
     const float* src = P + a.woff[l];

@@ -28,8 +28,8 @@ int qnet_layout(const drl_qnet_desc* d, drl::QnetLayout* L) {
         return fail("in_features must be even and in [4, 512]");
     if (d->n_hidden < 1 || d->n_hidden > 3) return fail("n_hidden must be 1, 2 or 3");
     for (int i = 0; i < d->n_hidden; ++i)
-        if (d->hidden[i] < 32 || d->hidden[i] > 128 || d->hidden[i] % 32)
-            return fail("hidden widths must be multiples of 32 in [32, 128]");
+        if (d->hidden[i] < 8 || d->hidden[i] > 128 || d->hidden[i] % 8)
+            return fail("hidden widths must be multiples of 8 in [8, 128]");
     if (d->n_actions < 1 || d->n_actions > 8) return fail("n_actions must be in [1, 8]");
     if (d->precision != DRL_QNET_BF16 && d->precision != DRL_QNET_F32)
         return fail("precision must be DRL_QNET_BF16 or DRL_QNET_F32");
@@ -50,11 +50,13 @@ int qnet_layout(const drl_qnet_desc* d, drl::QnetLayout* L) {
     for (int l = 0; l < L->n_layers; ++l) {
         L->in[l] = l == 0 ? d->in_features : d->hidden[l - 1];
         L->out[l] = l < d->n_hidden ? d->hidden[l] : d->n_actions;
-        L->nt[l] = (L->out[l] + 15) / 16;  // 16-row MFMA tiles
-        // 32-wide K-slices; layer 0 padded to a multiple of the act kernel's slice ring
+        // 16-row MFMA tiles.  A hidden layer is laid out for its width rounded up to 32 (a pair of tiles is
+        // one K-slice of the next layer: the act kernels' kt = nt_prev / 2); the rows past `out` are pads
+        L->nt[l] = l < d->n_hidden ? 2 * ((L->out[l] + 31) / 32) : (L->out[l] + 15) / 16;
+        // 32-wide K-slices (the k past `in` are pads); layer 0 padded to a multiple of the act kernel's slice ring
         constexpr int R = drl::lay::qn_ring;
         L->kt[l] = l == 0 ? (code_w ? drl::lay::code_kt(code_w) : ((d->in_features + 31) / 32 + R - 1) / R * R)
-                          : L->in[l] / 32;
+                          : (L->in[l] + 31) / 32;
         L->frag_off[l] = frag * 64;
         L->frag_src[l] = frag * 64;
         L->bias_off[l] = bias;
@@ -165,6 +167,11 @@ static uint32_t rm_of(int row) { return row > 1 ? drl::make_fastdiv((uint32_t)ro
 
 static int dqn_plan(const drl_qnet_desc* d, int32_t batch, const drl::QnetLayout& L, DqnPlan* P) {
     if (batch < 1 || batch > drl::DQN_MAX_BATCH) return fail("batch must be in [1, 64]");
+    // what the kernel takes from the hidden widths, all given by qnet_layout's rule (multiples of 8 up to 128):
+    // whole DQN_TILE-unit layer-0 tiles (% DQN_TILE) and 16-B rows of the published activations and deltas
+    // (dq_publish: % 4); whole float2s per weight row of the prefetched tail (in % 2) at even LDS offsets
+    // (region_a = 2 B maxw + (L - 1) B maxw / 4 is even for every B only with maxw % 8 == 0: the binding one);
+    // a layer-0 tile's W_1 columns within W1R registers per thread and s_gb's 128 bias gradients (<= 128)
     memset(P, 0, sizeof *P);
     drl_dqn_layout& o = P->pub;
     int64_t f = 0;

@@ -117,6 +117,10 @@ def _stream(device):
 class QNetwork:
     """Dense Q-network: in_features -> hidden... (ReLU) -> n_actions.
 
+    hidden: 1 to 3 widths, each a multiple of 8 in [8, 128] (the reference's
+    default (16, 16) net included; the packed image pads a width to the next
+    multiple of 32 with zeros, include/dronerl.h drl_qnet_desc).
+
     precision "f32" (the default): the reference's f32 nets (jax
     dqn.py:47-63, torch dqn.py:44-82): split fp16 hi/lo operands, three MFMAs
     per product tile, Q to f32 rounding (include/dronerl.h DRL_QNET_F32).

@@ -42,7 +42,8 @@ def train(params: EnvParams, num_envs: int, num_steps: int, hidden: Sequence[int
           group=None) -> TrainResult:
     """train_jax.py's training loop (see the module docstring).  hp: a
     dqn.DQNHParams (default: train_jax.py's defaults with num_steps, so
-    epsilon decays as :133-134 schedules it).
+    epsilon decays as :133-134 schedules it).  hidden: 1-3 widths, each a
+    multiple of 8 in [8, 128] (train_jax.py's default net is (16, 16)).
 
     world > 1 (one process per GPU, an initialised torch.distributed group):
     train_jax.py --use_sharding (:196-212) -- this rank steps envs
@@ -132,10 +133,12 @@ def evaluate(params: EnvParams, qnet, num_evals: int = 5, num_eval_steps: int = 
 def parse_args(argv=None):
     """train_jax.py's command line (:335-390) for the options this driver
     implements: the env, training and eval options and
-    --save_final_checkpoint; the dense net's widths must be multiples of 32
-    in [32, 128] (the device act's tiles), so --hidden_layers defaults to the
-    benchmark net (128, 64) instead of (16, 16).  --use_sharding runs under
-    torchrun (one process per GPU)."""
+    --save_final_checkpoint; the dense net's widths are multiples of 8 in
+    [8, 128] (1-3 layers), so train_jax.py's default `--hidden_layers 16 16`
+    runs as it is.  --hidden_layers here defaults to the benchmark net
+    (128, 64): a choice (what this command has always trained), no longer a
+    limit of the device act.  --use_sharding runs under torchrun (one process
+    per GPU)."""
     import argparse
     ap = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     ap.add_argument("--n_drones", type=int, default=4)

@@ -371,7 +371,8 @@ int drl_env_errors(drl_env* env, int32_t* flags, int32_t clear, hipStream_t stre
 typedef struct drl_qnet_desc {
     int32_t in_features;  /* observation floats, W*W*6 (even, <= 512) */
     int32_t n_hidden;     /* 1..3 hidden layers */
-    int32_t hidden[3];    /* widths: multiples of 32 in [32, 128] */
+    int32_t hidden[3];    /* widths: multiples of 8 in [8, 128] (the packed image pads each to the next
+                           * multiple of 32 with zero rows, columns and biases) */
     int32_t n_actions;    /* 1..8 (Action.num_actions() = 5) */
     int32_t precision;    /* DRL_QNET_BF16 or DRL_QNET_F32 */
     int32_t input;        /* DRL_QNET_INPUT_OBS or DRL_QNET_INPUT_CODE (ABI 7) */
