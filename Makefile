@@ -16,8 +16,9 @@ HOSTSAN := -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined \
            -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer
 CSRC := dronerl_amd/csrc
 SRCS := $(CSRC)/dronerl_kernels.hip $(CSRC)/dronerl_api.cpp $(CSRC)/dronerl_env.cpp $(CSRC)/dronerl_qnet.hip \
-        $(CSRC)/dronerl_qnet_api.cpp $(CSRC)/dronerl_learn.hip
-DEPS := $(SRCS) $(CSRC)/dronerl_internal.h include/dronerl.h
+        $(CSRC)/dronerl_qnet_api.cpp $(CSRC)/dronerl_learn.hip $(CSRC)/convnet/dronerl_convnet.hip \
+        $(CSRC)/convnet/dronerl_convnet_api.cpp
+DEPS := $(SRCS) $(CSRC)/dronerl_internal.h $(CSRC)/convnet/dronerl_convnet_layout.h include/dronerl.h
 
 asan: build/asan/liboracle.so build/asan/libdronerl.so
 

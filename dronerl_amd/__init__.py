@@ -13,7 +13,8 @@ Semantics are torch_impl's, bit-exact.  See DESIGN.md and INTEGRATION.md.
 from .constants import Action, Object
 from .params import EnvParams, side_from_density
 
-__all__ = ["Action", "Object", "EnvParams", "side_from_density", "BatchedDeliveryDrones", "DroneEnvState"]
+__all__ = ["Action", "Object", "EnvParams", "side_from_density", "BatchedDeliveryDrones", "DroneEnvState",
+           "QNetwork", "ConvQNetwork"]
 
 
 def __getattr__(name):
@@ -21,4 +22,7 @@ def __getattr__(name):
     if name in ("BatchedDeliveryDrones", "DroneEnvState"):
         from . import env
         return getattr(env, name)
+    if name in ("QNetwork", "ConvQNetwork"):  # the on-device Q-networks (dense; conv: inference only)
+        from . import dqn
+        return getattr(dqn, name)
     raise AttributeError(name)

@@ -206,13 +206,28 @@ def save_dense(path: str, weights, biases, obs_shape, format: str = "torch", con
     save_file(t, path, metadata=md)
 
 
-def to_qnet(ck: Checkpoint, device=None):
-    """A dense checkpoint on the MFMA consumer (dronerl_amd.dqn.QNetwork).
-    Needs hidden widths that are multiples of 8 in [8, 128] (1-3 layers): the
-    reference's default (16, 16) net among them."""
-    from .dqn import QNetwork
-    if ck.network_type != "dense":
-        raise ValueError("only dense networks run on the MFMA consumer")
+def to_qnet(ck: Checkpoint, device=None, input: str = "obs"):
+    """A checkpoint on the MFMA consumer: a dense one as
+    dronerl_amd.dqn.QNetwork (hidden widths multiples of 8 in [8, 128], 1-3
+    layers: the reference's default (16, 16) net among them), a conv one
+    (torch or jax format: read_checkpoint yields torch layouts for both) as
+    dronerl_amd.dqn.ConvQNetwork (its limits: include/dronerl.h
+    drl_convnet_desc).  input "code": the net acts from the policy code."""
+    from .dqn import ConvQNetwork, QNetwork
+    if ck.network_type == "conv":
+        if any(w % 8 or not 8 <= w <= 128 for w in ck.dense_layers):
+            raise ValueError(f"dense widths {ck.dense_layers} unsupported by drl_convnet (multiples of 8 in [8, 128])")
+        net = ConvQNetwork(ck.obs_shape, ck.conv_layers, ck.dense_layers, int(ck.action_shape[0]), device=device,
+                           input=input)
+        t = lambda name: torch.from_numpy(np.array(ck.tensors[name]))  # noqa: E731
+        nc, nd = len(ck.conv_layers), len(ck.dense_layers) + 1
+        net.load([t(f"network.conv2d_{i + 1}.weight") for i in range(nc)],
+                 [t(f"network.conv2d_{i + 1}.bias") for i in range(nc)],
+                 [t(f"network.dense_{i + 1}.weight") for i in range(nd)],
+                 [t(f"network.dense_{i + 1}.bias") for i in range(nd)])
+        return net
+    if input != "obs":
+        raise ValueError("input='code' for a dense checkpoint: build a QNetwork(input='code') and load it")
     if not ck.dense_layers or len(ck.dense_layers) > 3 or any(w % 8 or not 8 <= w <= 128 for w in ck.dense_layers):
         raise ValueError(f"hidden widths {ck.dense_layers} unsupported by drl_qnet (multiples of 8 in [8, 128])")
     n = len(ck.dense_layers) + 1

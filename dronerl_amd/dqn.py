@@ -293,6 +293,238 @@ class QNetwork:
             raise DroneRLError(f"qnet error bits {e:#x}")
 
 
+class DrlConvnetConv(ctypes.Structure):
+    _fields_ = [("out_channels", ctypes.c_int32), ("kernel_size", ctypes.c_int32), ("stride", ctypes.c_int32),
+                ("padding", ctypes.c_int32)]
+
+
+class DrlConvnetDesc(ctypes.Structure):
+    _fields_ = [("window", ctypes.c_int32), ("n_conv", ctypes.c_int32), ("conv", DrlConvnetConv * 3),
+                ("n_dense", ctypes.c_int32), ("dense", ctypes.c_int32 * 2), ("n_actions", ctypes.c_int32),
+                ("input", ctypes.c_int32)]
+
+
+def _bind_convnet(L):
+    if getattr(L, "_convnet_ready", False):
+        return L
+    i64, u64, f32 = ctypes.c_int64, ctypes.c_uint64, ctypes.c_float
+    D, PP = ctypes.POINTER(DrlConvnetDesc), ctypes.POINTER(_vp)
+    sig = {
+        "drl_convnet_packed_bytes": [D, ctypes.POINTER(i64)],
+        "drl_convnet_pack": [D, PP, PP, PP, PP, _vp, _vp],
+        "drl_convnet_act": [D, _vp, _vp, i64, i64, f32, _vp, u64, u64, i64, _vp, i64, _vp, _vp, _vp],
+    }
+    for name, args in sig.items():
+        f = getattr(L, name)
+        f.argtypes = args
+        f.restype = ctypes.c_int
+    L._convnet_ready = True
+    return L
+
+
+def _square(v, name):
+    """A reference conv_layers value (an int, or a tuple of two equal ints) as an int."""
+    if isinstance(v, (tuple, list)):
+        if len(set(v)) != 1:
+            raise ValueError(f"{name} must be square, got {tuple(v)}")
+        v = v[0]
+    if int(v) != v:
+        raise ValueError(f"{name} must be an integer")
+    return int(v)
+
+
+def convnet_desc(obs_shape, conv_layers, dense_layers=(), n_actions: int = NUM_ACTIONS, input: str = "obs"):
+    """The drl_convnet_desc of a reference conv net: obs_shape (W, W, 6), conv_layers the reference's tuple of
+    dicts (out_channels, kernel_size; stride 1 and padding 0 by default, jax dqn.py:66-94).  The limits
+    themselves are checked by the library (drl_convnet_packed_bytes names the field)."""
+    if input not in INPUTS:
+        raise ValueError(f"input must be one of {sorted(INPUTS)}")
+    obs_shape = tuple(int(v) for v in obs_shape)
+    if len(obs_shape) != 3 or obs_shape[0] != obs_shape[1] or obs_shape[2] != 6:
+        raise ValueError(f"obs_shape must be (W, W, 6), got {obs_shape}")
+    conv_layers, dense_layers = tuple(conv_layers), tuple(int(w) for w in dense_layers)
+    if not 1 <= len(conv_layers) <= 3:
+        raise ValueError("conv_layers: 1 to 3 conv layers (n_conv)")
+    if len(dense_layers) > 2:
+        raise ValueError("dense_layers: at most 2 hidden dense layers (n_dense)")
+    conv = (DrlConvnetConv * 3)()
+    for i, c in enumerate(conv_layers):
+        unknown = set(c) - {"out_channels", "kernel_size", "stride", "padding"}
+        if unknown:
+            raise ValueError(f"conv layer {i}: unsupported keys {sorted(unknown)}")
+        conv[i] = DrlConvnetConv(int(c["out_channels"]), _square(c["kernel_size"], "kernel_size"),
+                                 _square(c.get("stride", 1), "stride"), _square(c.get("padding", 0), "padding"))
+    return DrlConvnetDesc(obs_shape[0], len(conv_layers), conv, len(dense_layers),
+                          (ctypes.c_int32 * 2)(*dense_layers, *[0] * (2 - len(dense_layers))), int(n_actions),
+                          INPUTS[input])
+
+
+class ConvQNetwork:
+    """Convolutional Q-network, the inference half (torch_impl dqn.py:85-159 /
+    jax dqn.py:66-94 ConvQNetwork): Conv2d + ReLU per conv layer on the
+    [W, W, 6] window, the flatten in torch's channel-major order, 0 to 2
+    hidden Dense + ReLU, Dense(n_actions).  `act` runs the forward and the
+    epsilon-greedy choice for every env in one launch (drl_convnet_act, f32
+    numerics as QNetwork's "f32"), with QNetwork.act's exploration stream:
+    the same (seed, step, env_offset) explores on the same envs with the same
+    random actions.  Training conv nets on the device is not implemented.
+
+    conv_layers: the reference's tuple of dicts, e.g. ({"out_channels": 8,
+    "kernel_size": 3, "stride": 1, "padding": 1},); stride defaults to 1 and
+    padding to 0.  Limits (include/dronerl.h drl_convnet_desc): W odd in
+    [3, 9]; 1-3 conv layers, out_channels 1-32, square kernels 1-5, stride
+    1-3, padding 0-4; 0-2 dense widths, multiples of 8 in [8, 128]; 1-8
+    actions.  input "code" (W in 5, 7, 9): `act` reads drone 0's policy code;
+    Q is bit for bit the "obs" net's.
+
+    conv_weights [out][in][kh][kw] / conv_biases and weights [out][in] /
+    biases (the dense tail, the Q head last) are f32 device tensors in torch
+    layout, initialised as the reference's jax net (flax Conv / Dense default
+    lecun_normal, zero biases)."""
+
+    def __init__(self, obs_shape, conv_layers, dense_layers: Sequence[int] = (), n_actions: int = NUM_ACTIONS,
+                 device=None, generator: Optional[torch.Generator] = None, input: str = "obs"):
+        self.desc = convnet_desc(obs_shape, conv_layers, dense_layers, n_actions, input)
+        self.L = _bind_convnet(lib())
+        nb = ctypes.c_int64()
+        if self.L.drl_convnet_packed_bytes(ctypes.byref(self.desc), ctypes.byref(nb)):
+            raise ValueError(self.L.drl_last_error().decode())
+        self.input = input
+        self.obs_shape = tuple(int(v) for v in obs_shape)
+        self.window = self.obs_shape[0]
+        self.in_features = self.window * self.window * 6
+        self.conv_layers = tuple({"out_channels": int(c.out_channels), "kernel_size": int(c.kernel_size),
+                                  "stride": int(c.stride), "padding": int(c.padding)}
+                                 for c in self.desc.conv[:self.desc.n_conv])
+        self.dense_layers, self.n_actions = tuple(int(w) for w in dense_layers), int(n_actions)
+        self.code_bytes = int(lib().drl_policy_code_bytes((self.window - 1) // 2)) if input == "code" else 0
+        self.device = torch.device(device if device is not None else "cuda")
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.conv_weights, self.conv_biases, self.weights, self.biases = [], [], [], []
+        side, cin = self.window, 6
+        for c in self.conv_layers:
+            k, co = c["kernel_size"], c["out_channels"]
+            # flax Conv's lecun_normal: fan_in = kh * kw * in
+            w = flax_kernel_init((co, cin * k * k), 1.0, generator).reshape(co, cin, k, k)
+            self.conv_weights.append(w.to(self.device))
+            self.conv_biases.append(torch.zeros(co, device=self.device))
+            side, cin = (side + 2 * c["padding"] - k) // c["stride"] + 1, co
+        self.flat = side * side * cin
+        sizes = [self.flat, *self.dense_layers, self.n_actions]
+        for i in range(len(sizes) - 1):
+            self.weights.append(flax_kernel_init((sizes[i + 1], sizes[i]), 1.0, generator).to(self.device))
+            self.biases.append(torch.zeros(sizes[i + 1], device=self.device))
+        self.packed = torch.empty(nb.value // 4, dtype=torch.int32, device=self.device)  # 16-B aligned
+        self.err = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.pack()
+
+    def _validate(self, *groups):
+        for t in (t for grp in groups for t in grp):
+            if not bool(torch.isfinite(t).all()):
+                raise ValueError("weights and biases must be finite")
+        for t in (*groups[0], *groups[2]):  # the weights are split into fp16 pieces; the biases stay f32
+            if float(t.abs().max()) >= 65504.0:
+                raise ValueError("the f32 act needs |w| < 65504")
+
+    def load(self, conv_weights, conv_biases, weights, biases):
+        """Set parameters (torch layouts) and re-pack.  Nothing changes if
+        they are refused."""
+        new = []
+        for name, given, mine in (("conv_weights", conv_weights, self.conv_weights),
+                                  ("conv_biases", conv_biases, self.conv_biases),
+                                  ("weights", weights, self.weights), ("biases", biases, self.biases)):
+            if len(given) != len(mine):
+                raise ValueError(f"{name}: layer count mismatch")
+            for i, (t, m) in enumerate(zip(given, mine)):
+                if tuple(t.shape) != tuple(m.shape):
+                    raise ValueError(f"{name}[{i}]: shape {tuple(t.shape)} != {tuple(m.shape)}")
+            new.append([t.detach().to(self.device, torch.float32) for t in given])
+        self._validate(*new)
+        for mine, ts in zip((self.conv_weights, self.conv_biases, self.weights, self.biases), new):
+            for m, t in zip(mine, ts):
+                m.copy_(t)
+        self.pack()
+
+    def pack(self):
+        self._validate(self.conv_weights, self.conv_biases, self.weights, self.biases)
+        ptrs = [(_vp * len(ts))(*[t.data_ptr() for t in ts])
+                for ts in (self.conv_weights, self.conv_biases, self.weights, self.biases)]
+        _check(self.L, self.L.drl_convnet_pack(ctypes.byref(self.desc), *ptrs, _vp(self.packed.data_ptr()),
+                                               _stream(self.device)))
+
+    def reference_q(self, obs: torch.Tensor) -> torch.Tensor:
+        """Plain torch f32 forward (checker for tests): the reference's
+        ConvQNetwork.forward on obs [E, W, W, 6]."""
+        W = self.window
+        x = obs.reshape(obs.shape[0], -1)[:, :self.in_features].to(torch.float32).reshape(-1, W, W, 6).permute(0, 3, 1, 2)
+        for c, w, b in zip(self.conv_layers, self.conv_weights, self.conv_biases):
+            # conv2d as im2col + matmul (the same sums; no convolution library involved)
+            k, s, p = c["kernel_size"], c["stride"], c["padding"]
+            side = (x.shape[2] + 2 * p - k) // s + 1
+            cols = torch.nn.functional.unfold(x, k, padding=p, stride=s)  # [E, cin*k*k, side*side]
+            x = torch.relu(w.to(x.device).reshape(w.shape[0], -1) @ cols + b.to(x.device)[:, None])
+            x = x.reshape(x.shape[0], w.shape[0], side, side)
+        x = x.flatten(1)
+        for i, (w, b) in enumerate(zip(self.weights, self.biases)):
+            x = x @ w.to(x.device).t() + b.to(x.device)
+            if i < len(self.weights) - 1:
+                x = torch.relu(x)
+        return x
+
+    def act(self, obs: torch.Tensor, epsilon, seed: int = 0, step: int = 0, env_offset: int = 0,
+            actions: Optional[torch.Tensor] = None, q_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Epsilon-greedy action for each row of obs [E, ..., W*W*6] (input
+        "code": the policy code, uint8 [E, code_bytes]); the arguments and the
+        return value are QNetwork.act's.  epsilon: a float, or a float32
+        device tensor of one element read by the kernel."""
+        E = obs.shape[0]
+        if self.input == "code":
+            _on(obs, self.device, torch.uint8, "code")
+            if tuple(obs.shape) != (E, self.code_bytes) or not obs.is_contiguous():
+                raise ValueError(f"code must be a contiguous uint8 [E, {self.code_bytes}] tensor")
+            x, stride = obs, 0
+        else:
+            _on(obs, self.device, torch.float32, "obs")
+            x = obs.reshape(E, -1)
+            if x.shape[1] < self.in_features or x.stride(1) != 1:
+                raise ValueError("obs must hold at least W*W*6 contiguous float32 values per env")
+            stride = x.stride(0)
+        if actions is None:
+            actions = torch.empty((E, 1), dtype=torch.int32, device=self.device)
+        _on(actions, self.device, torch.int32, "actions")
+        if actions.shape[0] != E or actions.dim() > 2 or not actions.is_contiguous():
+            raise ValueError("actions must be a contiguous int32 [E] or [E, n] tensor")
+        if q_out is not None:
+            _on(q_out, self.device, torch.float32, "q_out")
+            if tuple(q_out.shape) != (E, self.n_actions) or not q_out.is_contiguous():
+                raise ValueError(f"q_out must be a contiguous float32 [{E}, {self.n_actions}] tensor")
+        stride_a = actions.shape[1] if actions.dim() == 2 else 1
+        eps_ptr = None
+        if isinstance(epsilon, torch.Tensor):
+            _on(epsilon, self.device, torch.float32, "epsilon")
+            if epsilon.numel() != 1:
+                raise ValueError("a device epsilon must be one float32 element")
+            eps_ptr, epsilon = _vp(epsilon.data_ptr()), 0.0
+        _check(self.L, self.L.drl_convnet_act(
+            ctypes.byref(self.desc), _vp(self.packed.data_ptr()), _vp(x.data_ptr()), E, stride, float(epsilon),
+            eps_ptr, seed & (2**64 - 1), step, env_offset, _vp(actions.data_ptr()), stride_a,
+            None if q_out is None else _vp(q_out.data_ptr()), _vp(self.err.data_ptr()), _stream(self.device)))
+        return actions
+
+    def check_errors(self):
+        """Synchronise and raise if an act met a staged input or an
+        activation outside fp16's split range (|v| >= 65520, or NaN): its Q
+        values and greedy actions are then not valid (DRL_ERR_QNET_RANGE)."""
+        e = int(self.err.item())
+        if e:
+            self.err.zero_()
+            if e & DRL_ERR_QNET_RANGE:
+                raise DroneRLError("conv act: an input or activation is outside the fp16 split range "
+                                   "(|v| >= 65520 or NaN); Q values are not valid")
+            raise DroneRLError(f"convnet error bits {e:#x}")
+
+
 def decode_policy_code(code: torch.Tensor, window_radius: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Policy-code rows uint8 [n, code_bytes] -> drone 0's observation f32
     [n, W*W*6], bit for bit what drl_obs writes (drl_code_decode)."""

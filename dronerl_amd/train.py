@@ -165,7 +165,9 @@ def parse_args(argv=None):
     ap.add_argument("--tau", type=float, default=1.0)
     ap.add_argument("--save_final_checkpoint", action="store_true", default=False)
     ap.add_argument("--use_sharding", action="store_true", default=False)
-    ap.add_argument("--network_type", choices=["dense"], default="dense")
+    ap.add_argument("--network_type", choices=["dense"], default="dense",
+                    help="conv Q-networks act on the device (dronerl_amd.dqn.ConvQNetwork, checkpoint.to_qnet) "
+                         "but do not train there yet")
     ap.add_argument("--hidden_layers", nargs="+", type=int, default=(128, 64))
     ap.add_argument("--pickup_reward", type=float, default=0.0)
     ap.add_argument("--delivery_reward", type=float, default=1.0)

@@ -587,6 +587,69 @@ int drl_dqn_train_fresh(const drl_qnet_desc* d, const drl_dqn_hparams* h, void* 
 int drl_dqn_sample_rows(const drl_qnet_desc* d, const drl_dqn_hparams* h, const void* d_agent, int64_t size,
                         int64_t* d_slots, hipStream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Convolutional Q-networks, the inference half (torch_impl/agents/dqn.py:85-159
+ * ConvQNetwork, jax_impl/agents/dqn.py:66-94; sample_models/dqn-agent-5 is one):
+ *   x: [E][W][W][6] f32 window (drl_obs's layout, channels last)
+ *   per conv layer: y[oy][ox][co] = relu(b[co] + sum_{ky,kx,ci} w[co][ci][ky][kx]
+ *       * x[oy*s + ky - p][ox*s + kx - p][ci]), x = 0 outside the map, output
+ *       side (side + 2p - k) / s + 1 (floor);
+ *   flatten in torch order (co*H*W + oy*W + ox; jax dqn.py:82 transposes to the
+ *       same), 0..2 hidden Dense + ReLU, Dense(n_actions).
+ * Numerics are DRL_QNET_F32's (fp16 hi/lo split operands, three MFMAs per
+ * product tile): Q matches an f32 forward to f32 rounding.  Training conv
+ * nets is not part of this ABI.
+ * Limits (each refused by name when the description is validated, by every
+ * call below): window odd in [3, 9]; 1..3 conv layers with out_channels in
+ * [1, 32], square kernel_size in [1, 5], stride in [1, 3], padding in [0, 4],
+ * every map side >= 1; 0..2 dense widths, multiples of 8 in [8, 128];
+ * n_actions in [1, 8]; input DRL_QNET_INPUT_OBS or DRL_QNET_INPUT_CODE (a
+ * 5x5, 7x7 or 9x9 window); one env's maps (with their zero halos) within the
+ * 160 KB LDS of a CU.
+ * ------------------------------------------------------------------------ */
+#define DRL_CONVNET_MAX_CONV 3
+#define DRL_CONVNET_MAX_DENSE 2
+typedef struct drl_convnet_conv {
+    int32_t out_channels, kernel_size, stride, padding;
+} drl_convnet_conv;
+typedef struct drl_convnet_desc {
+    int32_t window;   /* W: the observation is [W][W][6] */
+    int32_t n_conv;
+    drl_convnet_conv conv[DRL_CONVNET_MAX_CONV];
+    int32_t n_dense;  /* hidden dense layers after the flatten (0: the flatten feeds the Q head) */
+    int32_t dense[DRL_CONVNET_MAX_DENSE];
+    int32_t n_actions;
+    int32_t input;    /* DRL_QNET_INPUT_OBS or DRL_QNET_INPUT_CODE */
+} drl_convnet_desc;
+
+/* Bytes of the packed network (opaque: fp16 hi and lo MFMA fragments of every
+ * layer, f32 biases, the conv layers' gather tables, a status word). */
+int drl_convnet_packed_bytes(const drl_convnet_desc* d, int64_t* bytes);
+/* Pack the parameters (f32, torch layout): d_conv_w[l] [out][in][kh][kw] and
+ * d_conv_b[l] [out] for the n_conv conv layers, d_dense_w[l] [out][in] and
+ * d_dense_b[l] [out] for the n_dense + 1 dense layers (the Q head last); host
+ * arrays of device pointers.  The zero padding of every GEMM and the flatten's
+ * permutation (the first dense layer's columns) are folded into the image.  A
+ * weight with |w| >= 65504 (or not finite) sets the image's status word, which
+ * every act then reports as DRL_ERR_QNET_RANGE.  d_packed: 16-byte aligned. */
+int drl_convnet_pack(const drl_convnet_desc* d, const float* const* d_conv_w, const float* const* d_conv_b,
+                     const float* const* d_dense_w, const float* const* d_dense_b, void* d_packed, hipStream_t stream);
+/* drl_qnet_act's epsilon-greedy rule on the conv net's Q values, one launch
+ * for every env: the same counter hash of (seed, step, env_offset + e), the
+ * first maximum on ties.  d_input: f32 rows of obs_stride floats (8-byte
+ * aligned, obs_stride even and >= W*W*6) for a DRL_QNET_INPUT_OBS net; drone
+ * index 0's policy code (drl_policy_code_bytes per env, 16-byte aligned;
+ * obs_stride ignored) for a DRL_QNET_INPUT_CODE net, decoded exactly as
+ * drl_code_decode does, so Q is bit for bit the obs net's.  d_epsilon
+ * (nullable): the exploration rate read on the device instead of `epsilon`.
+ * d_q (nullable): f32 [num_envs][n_actions].  d_err (nullable): OR-ed
+ * DRL_ERR_QNET_RANGE when a staged input or an activation has |v| >= 65520 or
+ * is NaN.  Allocates nothing and does not synchronise. */
+int drl_convnet_act(const drl_convnet_desc* d, const void* d_packed, const void* d_input, int64_t num_envs,
+                    int64_t obs_stride, float epsilon, const float* d_epsilon, uint64_t seed, uint64_t step,
+                    int64_t env_offset, int32_t* d_actions, int64_t action_stride, float* d_q, int32_t* d_err,
+                    hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
