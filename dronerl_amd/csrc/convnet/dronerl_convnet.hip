@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "../dronerl_internal.h"
+#include "../dronerl_act_common.h"
 #include "dronerl_convnet_layout.h"
 
 namespace drl {
@@ -78,13 +79,6 @@ __device__ __forceinline__ float cv_div100(int c) {
     const float q = x * r;
     const float e = __fmaf_rn(-q, 100.0f, x);
     return __fmaf_rn(e, r, q);
-}
-
-__device__ __forceinline__ uint64_t cv_splitmix64(uint64_t z) {
-    z += 0x9e3779b97f4a7c15ull;
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    return z ^ (z >> 31);
 }
 
 // ------------------------------------------------------------------ pack ---
@@ -321,36 +315,16 @@ __global__ void __launch_bounds__(kThreads) drl_convnet_act_kernel(ActArgs a) {
             }
             __syncthreads();
         }
-        if (tid < G && env0 + tid < a.E) {  // drl_qnet_act's rule (dronerl_qnet.hip)
-            const int64_t env = env0 + tid;
+        if (tid < G && env0 + tid < a.E) {  // the dense acts' epilogue (dronerl_act_common.h)
             const float* qv = reinterpret_cast<const float*>(act + tid * EW + L.q_reg);
             float q[8];
 #pragma unroll
             for (int i = 0; i < 8; ++i) q[i] = i < L.n_actions ? qv[i] : 0.0f;
-            int best = 0;
-            float qb = q[0];  // (q[i] > q[best] ? i : best, the first maximum, without a register-array index)
-#pragma unroll
-            for (int i = 1; i < 8; ++i)
-                if (i < L.n_actions && q[i] > qb) {
-                    qb = q[i];
-                    best = i;
-                }
-            const uint64_t ge = (uint64_t)(a.env_offset + env);
-            const uint64_t hsh = cv_splitmix64(a.seed ^ cv_splitmix64((a.step << 40) ^ (ge << 8) ^ 0xa5ull));
-            const float u = (float)(hsh >> 40) * (1.0f / 16777216.0f);
-            const int rnd = (int)(((hsh & 0xffffffffull) * (uint64_t)L.n_actions) >> 32);
-            const float eps = a.eps_ptr ? *a.eps_ptr : a.epsilon;
-            a.actions[env * a.action_stride] = (u < eps) ? rnd : best;
-            if (a.q) {
-#pragma unroll
-                for (int i = 0; i < 8; ++i)
-                    if (i < L.n_actions) a.q[env * L.n_actions + i] = q[i];
-            }
+            act_epilogue(a, env0 + tid, q, L.n_actions);
         }
         __syncthreads();  // (the next pass rewrites the maps and the Q words)
     }
-    bad |= tid == 0 && a.packed[L.status] != 0u;  // the pack's range flag
-    if (__ballot(bad) && lane == 0 && a.err) atomicOr(a.err, DRL_ERR_QNET_RANGE);
+    flag_qnet_range(a.err, a.packed + L.status, bad, lane);
 }
 
 int launch_convnet_pack(const PackArgs& a, hipStream_t s) {

@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "dronerl_internal.h"
+#include "dronerl_act_common.h"
 
 namespace drl {
 
@@ -777,19 +778,6 @@ __device__ __forceinline__ void for_other_lanes(int v, F&& f) {
 // writer's registers would otherwise spill in the plain step at 64 VGPRs).
 // RING (with CODE): also land drone 0's transitions in a replay ring
 // (drl_step_code_replay, step_ring_sink).
-// The synthetic action stream (drl_synth_actions, the oracle's synth_actions): drone `drone` of global env
-// `genv` at (seed, step) -- a counter hash, so any kernel can draw any element.
-__device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
-    z += 0x9e3779b97f4a7c15ull;
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    return z ^ (z >> 31);
-}
-__device__ __forceinline__ int synth_action(uint64_t seed, uint64_t step, uint64_t genv, uint64_t drone) {
-    const uint64_t h = splitmix64(seed ^ splitmix64((step << 40) ^ (genv << 8) ^ drone));
-    return (int)(((h >> 32) * 5ull) >> 32);
-}
-
 template <int P, class GEO, bool ROLL, bool NT, bool CODE = false, bool RING = false>
 __device__ __forceinline__ void step_batch(const StepArgs& a, int64_t wenv0) {
     using GMask = typename GMaskT<P>::type;
@@ -2522,9 +2510,7 @@ __global__ void drl_synth_actions_kernel(uint64_t seed, uint64_t step, int64_t e
         env = (uint64_t)(env_offset + t / N);
         drone = (uint64_t)(t % N);
     }
-    const uint64_t ctr = (step << 40) ^ (env << 8) ^ drone;
-    const uint64_t h = splitmix64(seed ^ splitmix64(ctr));
-    out[t] = (int32_t)(((h >> 32) * 5ull) >> 32);
+    out[t] = synth_action(seed, step, env, drone);
 }
 
 // ---------------------------------------------------------------- launch ---

@@ -36,6 +36,7 @@
 #include <stdint.h>
 
 #include "dronerl_internal.h"
+#include "dronerl_act_common.h"
 
 // every product and sum of this file rounds on its own (no FMA contraction): the order oracle/dqn_learner.py restates
 #pragma clang fp contract(off)
@@ -54,17 +55,10 @@ namespace drl {
 
 namespace {
 
-__device__ __forceinline__ uint64_t dq_mix(uint64_t z) {
-    z += 0x9e3779b97f4a7c15ull;
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    return z ^ (z >> 31);
-}
-
 // buffers.py:79-90: B uniform indices in [0, current_size) (the reference draws
 // them with jax.random.randint; here a counter hash of (seed, step, row)).
 __device__ __forceinline__ int64_t dq_sample(uint64_t seed, int32_t step, int b, int64_t size) {
-    const uint64_t h = dq_mix(seed ^ dq_mix(((uint64_t)(uint32_t)step << 16) | (uint64_t)b));
+    const uint64_t h = splitmix64(seed ^ splitmix64(((uint64_t)(uint32_t)step << 16) | (uint64_t)b));
     return (int64_t)(((h >> 32) * (uint64_t)size) >> 32);
 }
 

@@ -24,22 +24,12 @@
 #include <type_traits>
 
 #include "dronerl_internal.h"
+#include "dronerl_act_common.h"
 
 namespace drl {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ uint64_t qn_splitmix64(uint64_t z) {
-    z += 0x9e3779b97f4a7c15ull;
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    return z ^ (z >> 31);
-}
-
-// The exploration rate: the argument, or the learner's device counter
-// (drl_qnet_act_eps).
-__device__ __forceinline__ float qn_eps(const QnetArgs& a) { return a.eps_ptr ? *a.eps_ptr : a.epsilon; }
 
 // K index within a 32-wide slice of fragment element j for lane group g (see
 // the header comment).
@@ -149,12 +139,7 @@ __global__ void __launch_bounds__(64 * QN_WAVES) drl_qnet_act_kernel(QnetArgs a)
     for (int i = 0; i < QN_RING; ++i)
 #pragma unroll
         for (int h = 0; h < TP; ++h) load_slice(row[h], i, raw[h][i]);
-    for (int v0 = wave * 64; v0 < a.lds_vec; v0 += 64 * QN_WAVES)
-        if (v0 + lane < a.lds_vec)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a.packed + v0 + lane),
-                                             (__attribute__((address_space(3))) void*)(wl + v0), 16, 0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
+    stage_packed_lds(wl, a.packed, a.lds_vec, wave, QN_WAVES, lane);
     const float* bias = reinterpret_cast<const float*>(wl + a.frag_total);
     const uint4* W0 = wl + a.frag_off[0];
 
@@ -245,48 +230,10 @@ __global__ void __launch_bounds__(64 * QN_WAVES) drl_qnet_act_kernel(QnetArgs a)
         // ---- Q values: actions 0..3 in registers 0..3 of the g = 0 lanes,
         // 4..7 in those of the g = 1 lanes (column = env)
 #pragma unroll
-        for (int h = 0; h < TP; ++h) {
-            float q[8];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float own = acc[h][0][i] + bprev[4 * g + i];
-                const float hi = __shfl(own, c + 16);  // g = 1 lane of this env
-                q[i] = own;
-                q[i + 4] = hi;
-            }
-            const int64_t env = (TP * grp + h) * 16 + c;
-            if (g == 0 && env < a.E) {
-                int best = 0;  // jnp.argmax: first maximum
-                for (int i = 1; i < a.n_actions; ++i) best = q[i] > q[best] ? i : best;
-                const uint64_t ge = (uint64_t)(a.env_offset + env);
-                const uint64_t hsh = qn_splitmix64(a.seed ^ qn_splitmix64((a.step << 40) ^ (ge << 8) ^ 0xa5ull));
-                const float u = (float)(hsh >> 40) * (1.0f / 16777216.0f);
-                const int rnd = (int)(((hsh & 0xffffffffull) * (uint64_t)a.n_actions) >> 32);
-                a.actions[env * a.action_stride] = (u < qn_eps(a)) ? rnd : best;
-                if (a.q)
-                    for (int i = 0; i < a.n_actions; ++i) a.q[env * a.n_actions + i] = q[i];
-            }
-        }
+        for (int h = 0; h < TP; ++h)
+            tile_act(a, (TP * grp + h) * 16 + c, lane, [&](int i) { return acc[h][0][i] + bprev[4 * g + i]; });
     }
-    if (a.synth_n > 1) {
-        // drl_synth_actions' columns 1..N-1 of this wave's envs, last: stores
-        // issued before the net's LDS-DMA wait (vmcnt counts them) would delay
-        // the first group
-        const uint32_t nd = (uint32_t)a.synth_n - 1u;
-        const uint32_t per = (uint32_t)(TP * 16) * nd;
-        for (int64_t gg = grp0; gg < ngroups; gg += gstride) {
-            for (uint32_t k = (uint32_t)lane; k < per; k += 64u) {
-                const uint32_t el = k / nd;
-                const int64_t env = TP * 16 * gg + el;
-                const uint64_t drone = 1u + (k - el * nd);
-                if (env < a.E) {
-                    const uint64_t ctr = (a.synth_step << 40) ^ ((uint64_t)(a.env_offset + env) << 8) ^ drone;
-                    const uint64_t h = qn_splitmix64(a.synth_seed ^ qn_splitmix64(ctr));
-                    a.actions[env * a.action_stride + (int64_t)drone] = (int32_t)(((h >> 32) * 5ull) >> 32);
-                }
-            }
-        }
-    }
+    synth_tail<TP * 16>(a, grp0, ngroups, gstride, lane);
 }
 
 // ---------------------------------------------------------- act, F32 ---
@@ -379,12 +326,7 @@ __global__ void __launch_bounds__(64 * QN_WAVES) drl_qnet_act_f32_kernel(QnetArg
     for (int i = 0; i < QN_RING; ++i)
 #pragma unroll
         for (int h = 0; h < TP; ++h) load_slice(row[h], i, raw[h][i]);
-    for (int v0 = wave * 64; v0 < a.lds_vec; v0 += 64 * QN_WAVES)
-        if (v0 + lane < a.lds_vec)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a.packed + v0 + lane),
-                                             (__attribute__((address_space(3))) void*)(wl + v0), 16, 0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
+    stage_packed_lds(wl, a.packed, a.lds_vec, wave, QN_WAVES, lane);
     bool bad = false;  // an operand outside fp16's range (split_f16)
     const float* bias = LO0 ? reinterpret_cast<const float*>(a.packed + a.bias_vec)
                             : reinterpret_cast<const float*>(wl + a.frag_total);
@@ -496,46 +438,27 @@ __global__ void __launch_bounds__(64 * QN_WAVES) drl_qnet_act_f32_kernel(QnetArg
         }
 #pragma unroll
         for (int h = 0; h < TP; ++h) {
+            // (its own gather, argmax and Q store, not tile_act's: those reschedule this kernel's whole group
+            // loop, 44.5 against 41.9 us at 294 -> 128 -> 64, C3)
             float q[8];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const float own = (acc[h][0][i] + acl[h][0][i] * kLo) + bprev[4 * g + i];
-                const float hi = __shfl(own, c + 16);
-                q[i] = own;
-                q[i + 4] = hi;
+                q[i] = (acc[h][0][i] + acl[h][0][i] * kLo) + bprev[4 * g + i];
+                q[i + 4] = __shfl(q[i], c + 16);
             }
             const int64_t env = (TP * grp + h) * 16 + c;
             if (g == 0 && env < a.E) {
-                int best = 0;
+                int best = 0;  // jnp.argmax: first maximum
                 for (int i = 1; i < a.n_actions; ++i) best = q[i] > q[best] ? i : best;
-                const uint64_t ge = (uint64_t)(a.env_offset + env);
-                const uint64_t hsh = qn_splitmix64(a.seed ^ qn_splitmix64((a.step << 40) ^ (ge << 8) ^ 0xa5ull));
-                const float u = (float)(hsh >> 40) * (1.0f / 16777216.0f);
-                const int rnd = (int)(((hsh & 0xffffffffull) * (uint64_t)a.n_actions) >> 32);
-                a.actions[env * a.action_stride] = (u < qn_eps(a)) ? rnd : best;
+                store_act(a, env, explore_draw(a.seed, a.step, (uint64_t)(a.env_offset + env), a.n_actions, act_eps(a)),
+                          best);
                 if (a.q)
                     for (int i = 0; i < a.n_actions; ++i) a.q[env * a.n_actions + i] = q[i];
             }
         }
     }
-    bad |= lane == 0 && reinterpret_cast<const int32_t*>(a.packed + a.status_vec)[0] != 0;  // pack range flag
-    if (__ballot(bad) && lane == 0 && a.err) atomicOr(a.err, DRL_ERR_QNET_RANGE);
-    if (a.synth_n > 1) {  // as in drl_qnet_act_kernel
-        const uint32_t nd = (uint32_t)a.synth_n - 1u;
-        const uint32_t per = (uint32_t)(TP * 16) * nd;
-        for (int64_t gg = grp0; gg < ngroups; gg += gstride) {
-            for (uint32_t k = (uint32_t)lane; k < per; k += 64u) {
-                const uint32_t el = k / nd;
-                const int64_t env = TP * 16 * gg + el;
-                const uint64_t drone = 1u + (k - el * nd);
-                if (env < a.E) {
-                    const uint64_t ctr = (a.synth_step << 40) ^ ((uint64_t)(a.env_offset + env) << 8) ^ drone;
-                    const uint64_t h = qn_splitmix64(a.synth_seed ^ qn_splitmix64(ctr));
-                    a.actions[env * a.action_stride + (int64_t)drone] = (int32_t)(((h >> 32) * 5ull) >> 32);
-                }
-            }
-        }
-    }
+    flag_qnet_range(a.err, a.packed + a.status_vec, bad, lane);
+    synth_tail<TP * 16>(a, grp0, ngroups, gstride, lane);
 }
 
 // ----------------------------------------------------- act from the code ---
@@ -572,6 +495,11 @@ constexpr int QN_CODE_MAXW = DRL_QN_CODE_MAXW;
 #define DRL_QN_CODE_WAVES 8
 #endif
 constexpr int QN_CODE_WAVES = DRL_QN_CODE_WAVES;
+#ifdef DRL_QC_STAMPS  // diagnostic: the code acts write s_memtime stamps into q instead of Q (tools/time_act.py --stamps)
+constexpr bool kStoreQ = false;
+#else
+constexpr bool kStoreQ = true;
+#endif
 
 __device__ __forceinline__ float code_channel(uint32_t code, int ch) {
     const uint32_t obj = code & 7u, air = code >> 3;
@@ -586,10 +514,7 @@ __device__ __forceinline__ float code_channel(uint32_t code, int ch) {
     }
 }
 
-// NT1 > 0: the net has exactly two hidden layers, the second 16 * NT1 wide
-// (the benchmark's 294->128->64->5): the later layers' loops are compile-time,
-// so only the live accumulators hold registers (16 waves per CU fit).
-template <int NT0, bool LO0, int WN, int NT1>
+template <int NT0, bool LO0, int WN>
 __global__ void __launch_bounds__(64 * QN_CODE_MAXW) drl_qnet_act_code_kernel(QnetArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint4 wl[];
     constexpr int CPG = lay::code_cpg(WN), CPG8 = lay::code_cpg8(WN), CELLS = WN * WN;
@@ -621,14 +546,7 @@ __global__ void __launch_bounds__(64 * QN_CODE_MAXW) drl_qnet_act_code_kernel(Qn
 #endif
     const int64_t grp0 = (int64_t)blockIdx.x * nw + wave;
     int64_t grp = grp0;
-#ifndef DRL_DIAG_NO_WLOAD  // timing diagnostic (wrong results): no weight staging
-    for (int v0 = wave * 64; v0 < a.lds_vec; v0 += 64 * nw)
-        if (v0 + lane < a.lds_vec)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a.packed + v0 + lane),
-                                             (__attribute__((address_space(3))) void*)(wl + v0), 16, 0, 0);
-#endif
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
+    stage_packed_lds(wl, a.packed, a.lds_vec, wave, nw, lane);
     bool bad = false;
     const float* bias = LO0 ? reinterpret_cast<const float*>(a.packed + a.bias_vec)
                             : reinterpret_cast<const float*>(wl + a.frag_total);
@@ -640,9 +558,6 @@ __global__ void __launch_bounds__(64 * QN_CODE_MAXW) drl_qnet_act_code_kernel(Qn
     const auto pbuf = __builtin_amdgcn_make_buffer_rsrc((void*)a.packed, 0, a.total_bytes, 0x00020000);
     const int lane16 = lane * 16;
     auto frag_ld = [&](int frag_u4) __attribute__((always_inline)) {  // 64 lanes x 16 B at uint4 offset frag_u4
-#ifdef DRL_DIAG_QC_LDS_HIDDEN  // timing diagnostic (wrong results): hidden fragments from the LDS image
-        return wl[(frag_u4 & 0x3fff) + lane];
-#endif
         if constexpr (LO0) {
             const auto v = __builtin_amdgcn_raw_buffer_load_b128(pbuf, lane16, frag_u4 * 16, 0);
             uint4 r;
@@ -654,9 +569,6 @@ __global__ void __launch_bounds__(64 * QN_CODE_MAXW) drl_qnet_act_code_kernel(Qn
     };
     auto bias4 = [&](int off) __attribute__((always_inline)) {  // biases off + 4g .. off + 4g + 3
         f32x4 r;
-#ifdef DRL_DIAG_QC_NO_BIAS  // timing diagnostic (wrong results): no bias loads
-        return f32x4{0.01f * off, 0.0f, 0.0f, 0.0f};
-#endif
         if constexpr (LO0) {
             const auto v = __builtin_amdgcn_raw_buffer_load_b128(pbuf, 16 * g, a.bias_vec * 16 + off * 4, 0);
             __builtin_memcpy(&r, &v, 16);
@@ -691,11 +603,7 @@ __global__ void __launch_bounds__(64 * QN_CODE_MAXW) drl_qnet_act_code_kernel(Qn
                 float x = (sl == 6 * CPG && g == 0) ? 1.0f : 0.0f;  // the bias slot (drl_qnet_pack)
                 if (sl < 6 * CPG) {
                     const uint32_t cd = (cs[l >> 1] >> (16 * (l & 1))) & 0xffffu;
-#ifdef DRL_DIAG_QC_NO_DECODE  // timing diagnostics of the code act (wrong results)
-                    x = (float)(cd & 1u);
-#else
                     x = l < ncell_g ? code_channel(cd, ch) : 0.0f;
-#endif
                 }
                 bh[j] = (_Float16)x;
             }
@@ -708,13 +616,8 @@ __global__ void __launch_bounds__(64 * QN_CODE_MAXW) drl_qnet_act_code_kernel(Qn
             for (int m = 0; m < nt0; ++m) {
                 const f16x8 wh = as_f16x8(W0[(m * KP + ts) * 64 + lane]);
                 const f16x8 wo = as_f16x8(W0lo[(m * KP + ts) * 64 + lane]);
-#ifdef DRL_DIAG_QC_NO_L0MFMA
-                acc[m] = (t == 0 ? z4 : acc[m]) + (float)bh[m] + (float)wh[0] + (float)wo[1];
-                acl[m] = t == 0 ? z4 : acl[m];
-#else
                 acc[m] = MFMA_F16(wh, bh, t == 0 ? z4 : acc[m], 0, 0, 0);
                 acl[m] = MFMA_F16(wo, bh, t == 0 ? z4 : acl[m], 0, 0, 0);
-#endif
                 if (m % 4 == 3) __builtin_amdgcn_sched_barrier(0);  // <= 8 fragments in flight (registers)
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -724,11 +627,10 @@ __global__ void __launch_bounds__(64 * QN_CODE_MAXW) drl_qnet_act_code_kernel(Qn
 #ifdef DRL_QC_STAMPS
         const uint64_t ts1 = __builtin_amdgcn_s_memtime();
 #endif
-        // ---- hidden layers and the output layer: as drl_qnet_act_f32_kernel.
-        // layer(NTP, NTL, l): inputs from NTP accumulator tiles, NTL outputs
-        // (compile-time bounds; the generic path passes QN_MAXT and masks)
-        auto layer = [&](auto ntp_c, auto ntl_c, int l, int nt_prev, int nt_l) __attribute__((always_inline)) {
-            constexpr int NTP = decltype(ntp_c)::value, NTL = decltype(ntl_c)::value;
+        // ---- hidden layers and the output layer: as drl_qnet_act_f32_kernel
+        // (compile-time bounds QN_MAXT, masked by the layer's tile counts)
+        auto layer = [&](int l, int nt_prev, int nt_l) __attribute__((always_inline)) {
+            constexpr int NTP = QN_MAXT, NTL = QN_MAXT;
             const int bprev = a.bias_off[l - 1];
             f16x8 ah[NTP / 2], al[NTP / 2];
 #pragma unroll
@@ -765,114 +667,19 @@ __global__ void __launch_bounds__(64 * QN_CODE_MAXW) drl_qnet_act_code_kernel(Qn
                 __builtin_amdgcn_sched_barrier(0);  // fragment reads next to their MFMAs (register pressure)
             }
         };
-        int bprev;
-        if constexpr (NT1 > 0) {
-#ifndef DRL_DIAG_QC_NO_HIDDEN
-            // every fragment of a layer requested at once, one L2 round trip
-            // per layer (fragment by fragment the loads serialise on vmcnt)
-            constexpr int KT1 = NT0 / 2, KT2 = NT1 / 2;
-            uint4 f1h[KT1][NT1], f1l[KT1][NT1];
-            {
-                const int fl = a.frag_off[1], flo = a.frag_lo_off[1];
-#pragma unroll
-                for (int t = 0; t < KT1; ++t)
-#pragma unroll
-                    for (int m = 0; m < NT1; ++m) {
-                        f1h[t][m] = frag_ld(fl + (m * KT1 + t) * 64);
-                        f1l[t][m] = frag_ld(flo + (m * KT1 + t) * 64);
-                    }
-            }
-            f16x8 ah[KT1], al[KT1];
-#pragma unroll
-            for (int s2 = 0; s2 < KT1; ++s2) {
-                float v[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int m = 2 * s2 + (j >> 2), i = j & 3;
-                    v[j] = fmaxf(acc[m][i] + acl[m][i] * kLo, 0.0f);  // (bias folded into layer 0)
-                }
-                split_f16(v, ah[s2], al[s2], bad);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int t = 0; t < KT1; ++t)
-#pragma unroll
-                for (int m = 0; m < NT1; ++m) {
-                    const f16x8 wh = as_f16x8(f1h[t][m]), wo = as_f16x8(f1l[t][m]);
-                    acc[m] = MFMA_F16(wh, ah[t], t == 0 ? z4 : acc[m], 0, 0, 0);
-                    acl[m] = MFMA_F16(wh, al[t], t == 0 ? z4 : acl[m], 0, 0, 0);
-                    acl[m] = MFMA_F16(wo, ah[t], acl[m], 0, 0, 0);
-                }
-            __builtin_amdgcn_sched_barrier(0);
-            // the output layer: fragments and layer 1's biases at once
-            uint4 f2h[KT2], f2l[KT2];
-            f32x4 b1[KT2][2];
-            {
-                const int fl = a.frag_off[2], flo = a.frag_lo_off[2], bo = a.bias_off[1];
-#pragma unroll
-                for (int t = 0; t < KT2; ++t) {
-                    f2h[t] = frag_ld(fl + t * 64);
-                    f2l[t] = frag_ld(flo + t * 64);
-                    b1[t][0] = bias4(bo + 32 * t);
-                    b1[t][1] = bias4(bo + 32 * t + 16);
-                }
-            }
-            f16x8 ah2[KT2], al2[KT2];
-#pragma unroll
-            for (int s2 = 0; s2 < KT2; ++s2) {
-                float v[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int m = 2 * s2 + (j >> 2), i = j & 3;
-                    v[j] = fmaxf((acc[m][i] + acl[m][i] * kLo) + b1[s2][j >> 2][i], 0.0f);
-                }
-                split_f16(v, ah2[s2], al2[s2], bad);
-            }
-#pragma unroll
-            for (int t = 0; t < KT2; ++t) {
-                const f16x8 wh = as_f16x8(f2h[t]), wo = as_f16x8(f2l[t]);
-                acc[0] = MFMA_F16(wh, ah2[t], t == 0 ? z4 : acc[0], 0, 0, 0);
-                acl[0] = MFMA_F16(wh, al2[t], t == 0 ? z4 : acl[0], 0, 0, 0);
-                acl[0] = MFMA_F16(wo, ah2[t], acl[0], 0, 0, 0);
-            }
-#endif
-            bprev = a.bias_off[2];
-        } else {
-            int nt_prev = nt0;
-            for (int l = 1; l <= a.n_hidden; ++l) {
-                const int nt_l = (l < a.n_hidden) ? a.nt[l] : 1;
-                layer(std::integral_constant<int, QN_MAXT>{}, std::integral_constant<int, QN_MAXT>{}, l, nt_prev, nt_l);
-                nt_prev = nt_l;
-            }
-            bprev = a.bias_off[a.n_hidden];
+        int nt_prev = nt0;
+        for (int l = 1; l <= a.n_hidden; ++l) {
+            const int nt_l = (l < a.n_hidden) ? a.nt[l] : 1;
+            layer(l, nt_prev, nt_l);
+            nt_prev = nt_l;
         }
+        const int bprev = a.bias_off[a.n_hidden];
 #ifdef DRL_QC_STAMPS
         __builtin_amdgcn_sched_barrier(0);
         const uint64_t ts2 = __builtin_amdgcn_s_memtime();
 #endif
         const f32x4 bq = bias4(bprev);
-        float q[8];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float own = (acc[0][i] + acl[0][i] * kLo) + bq[i];
-            const float hi = __shfl(own, c + 16);
-            q[i] = own;
-            q[i + 4] = hi;
-        }
-        const int64_t env = grp * 16 + c;
-        if (g == 0 && env < a.E) {
-            int best = 0;
-            for (int i = 1; i < a.n_actions; ++i) best = q[i] > q[best] ? i : best;
-            const uint64_t ge = (uint64_t)(a.env_offset + env);
-            const uint64_t hsh = qn_splitmix64(a.seed ^ qn_splitmix64((a.step << 40) ^ (ge << 8) ^ 0xa5ull));
-            const float u = (float)(hsh >> 40) * (1.0f / 16777216.0f);
-            const int rnd = (int)(((hsh & 0xffffffffull) * (uint64_t)a.n_actions) >> 32);
-            a.actions[env * a.action_stride] = (u < qn_eps(a)) ? rnd : best;
-#ifndef DRL_QC_STAMPS
-            if (a.q)
-                for (int i = 0; i < a.n_actions; ++i) a.q[env * a.n_actions + i] = q[i];
-#endif
-        }
+        tile_act(a, grp * 16 + c, lane, [&](int i) { return (acc[0][i] + acl[0][i] * kLo) + bq[i]; }, kStoreQ);
 #ifdef DRL_QC_STAMPS
         const uint64_t ts3 = __builtin_amdgcn_s_memtime();
         if (lane == 0 && a.q) {
@@ -885,24 +692,8 @@ __global__ void __launch_bounds__(64 * QN_CODE_MAXW) drl_qnet_act_code_kernel(Qn
         }
 #endif
     }
-    bad |= lane == 0 && reinterpret_cast<const int32_t*>(a.packed + a.status_vec)[0] != 0;  // pack range flag
-    if (__ballot(bad) && lane == 0 && a.err) atomicOr(a.err, DRL_ERR_QNET_RANGE);
-    if (a.synth_n > 1) {  // as in drl_qnet_act_kernel (one 16-env tile per group)
-        const uint32_t nd = (uint32_t)a.synth_n - 1u;
-        const uint32_t per = 16u * nd;
-        for (int64_t gg = grp0; gg < ntiles; gg += gstride) {
-            for (uint32_t k = (uint32_t)lane; k < per; k += 64u) {
-                const uint32_t el = k / nd;
-                const int64_t env = 16 * gg + el;
-                const uint64_t drone = 1u + (k - el * nd);
-                if (env < a.E) {
-                    const uint64_t ctr = (a.synth_step << 40) ^ ((uint64_t)(a.env_offset + env) << 8) ^ drone;
-                    const uint64_t h = qn_splitmix64(a.synth_seed ^ qn_splitmix64(ctr));
-                    a.actions[env * a.action_stride + (int64_t)drone] = (int32_t)(((h >> 32) * 5ull) >> 32);
-                }
-            }
-        }
-    }
+    flag_qnet_range(a.err, a.packed + a.status_vec, bad, lane);
+    synth_tail<16>(a, grp0, ntiles, gstride, lane);
 }
 
 // drl_qnet_act_code for the two-hidden-layer nets of the benchmark shape
@@ -948,12 +739,7 @@ __global__ void __launch_bounds__(64 * QN_CODE2_WAVES) drl_qnet_act_code2_kernel
     uint32_t cw[TP][4 * NV];
 #pragma unroll
     for (int h = 0; h < TP; ++h) load_codes(TP * (grp < ngroups ? grp : 0) + h, cw[h]);
-    for (int v0 = wave * 64; v0 < a.lds_vec; v0 += 64 * nw)
-        if (v0 + lane < a.lds_vec)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a.packed + v0 + lane),
-                                             (__attribute__((address_space(3))) void*)(wl + v0), 16, 0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
+    stage_packed_lds(wl, a.packed, a.lds_vec, wave, nw, lane);
     bool bad = false;
     const uint4* W0 = wl + a.frag_off[0];
     const uint4* W0lo = LO0 ? wl + a.frag_lo_off[0] : a.packed + a.frag_lo_off[0];
@@ -1118,27 +904,19 @@ __global__ void __launch_bounds__(64 * QN_CODE2_WAVES) drl_qnet_act_code2_kernel
                 ql = MFMA_F16(wh, al2[t], t == 0 ? z4 : ql, 0, 0, 0);
                 ql = MFMA_F16(wo, ah2[t], ql, 0, 0, 0);
             }
+            // (its own epilogue, not tile_act: the rolled Q store keeps the 128-unit instances off the scratch)
             float q[8];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const float own = (qc[i] + ql[i] * kLo) + bq[i];
-                const float hi = __shfl(own, c + 16);
-                q[i] = own;
-                q[i + 4] = hi;
+                q[i] = (qc[i] + ql[i] * kLo) + bq[i];
+                q[i + 4] = __shfl(q[i], c + 16);
             }
             const int64_t env = (TP * grp + h) * 16 + c;
             if (g == 0 && env < a.E) {
-                int best = 0;
-                for (int i = 1; i < a.n_actions; ++i) best = q[i] > q[best] ? i : best;
-                const uint64_t ge = (uint64_t)(a.env_offset + env);
-                const uint64_t hsh = qn_splitmix64(a.seed ^ qn_splitmix64((a.step << 40) ^ (ge << 8) ^ 0xa5ull));
-                const float u = (float)(hsh >> 40) * (1.0f / 16777216.0f);
-                const int rnd = (int)(((hsh & 0xffffffffull) * (uint64_t)a.n_actions) >> 32);
-                a.actions[env * a.action_stride] = (u < qn_eps(a)) ? rnd : best;
-#ifndef DRL_QC_STAMPS
-                if (a.q)
+                const int explore = explore_draw(a.seed, a.step, (uint64_t)(a.env_offset + env), a.n_actions, act_eps(a));
+                store_act(a, env, explore, argmax_first(q, a.n_actions));
+                if (kStoreQ && a.q)
                     for (int i = 0; i < a.n_actions; ++i) a.q[env * a.n_actions + i] = q[i];
-#endif
             }
         }
 #ifdef DRL_QC_STAMPS
@@ -1154,24 +932,8 @@ __global__ void __launch_bounds__(64 * QN_CODE2_WAVES) drl_qnet_act_code2_kernel
         }
 #endif
     }
-    bad |= lane == 0 && reinterpret_cast<const int32_t*>(a.packed + a.status_vec)[0] != 0;  // pack range flag
-    if (__ballot(bad) && lane == 0 && a.err) atomicOr(a.err, DRL_ERR_QNET_RANGE);
-    if (a.synth_n > 1) {  // as in drl_qnet_act_kernel (TP 16-env tiles per group)
-        const uint32_t nd = (uint32_t)a.synth_n - 1u;
-        const uint32_t per = (uint32_t)(TP * 16) * nd;
-        for (int64_t gg = grp0; gg < ngroups; gg += gstride) {
-            for (uint32_t k = (uint32_t)lane; k < per; k += 64u) {
-                const uint32_t el = k / nd;
-                const int64_t env = TP * 16 * gg + el;
-                const uint64_t drone = 1u + (k - el * nd);
-                if (env < a.E) {
-                    const uint64_t ctr = (a.synth_step << 40) ^ ((uint64_t)(a.env_offset + env) << 8) ^ drone;
-                    const uint64_t hh = qn_splitmix64(a.synth_seed ^ qn_splitmix64(ctr));
-                    a.actions[env * a.action_stride + (int64_t)drone] = (int32_t)(((hh >> 32) * 5ull) >> 32);
-                }
-            }
-        }
-    }
+    flag_qnet_range(a.err, a.packed + a.status_vec, bad, lane);
+    synth_tail<TP * 16>(a, grp0, ngroups, gstride, lane);
 }
 
 // ------------------------------------- inline LDS reads of the code act ---
@@ -1239,29 +1001,8 @@ __device__ __forceinline__ f16x8 q3_f16(const q3u4 v) {
 #endif
 constexpr int QC4_PD = DRL_QC4_PD;  // layer-0 fragment reads in flight per wave (ring of QC4_PD + 2)
 constexpr int QC4_WAVES = 4;
-#ifndef DRL_QC4_PIN
-#define DRL_QC4_PIN 0  // A/B knob: empty-asm pins keeping each step's decode between its MFMAs
-#endif
-#ifndef DRL_QC4_EARLYVEC
-#define DRL_QC4_EARLYVEC 0  // A/B knob: slice 0 waits only for the first code vector of each tile
-#endif
-#ifndef DRL_QC4_DMALOOP
-#define DRL_QC4_DMALOOP 0  // A/B knob: stage slices >= 2 inside layer 0 (measured slower: 17.6 vs 16.5 us at C3)
-#endif
 #ifndef DRL_QC4_XCD
 #define DRL_QC4_XCD 0  // A/B knob: XCD-contiguous env groups (with the step's DRL_XCD_REMAP: codes read from the L2 they were written to)
-#endif
-#ifndef DRL_QC4_EARLYSPLIT
-#define DRL_QC4_EARLYSPLIT 1  // layer 1's first split inside layer 0's last slice (16.33-16.53 vs 16.44-16.75 us, g19)
-#endif
-#ifndef DRL_QC4_EARLYNEXT
-#define DRL_QC4_EARLYNEXT 0  // A/B knob: the second pass's codes loaded in the prologue (C5 act in the loop 41.4 vs 42.0 us, C3 loop 45.8 vs 45.1-45.4: not kept)
-#endif
-#ifndef DRL_QC4_IGLP1
-#define DRL_QC4_IGLP1 0  // A/B knob: sched_group_barrier MFMA / 3 VALU interleave of layer 1
-#endif
-#ifndef DRL_QC4_IGLP
-#define DRL_QC4_IGLP 0  // A/B knob: sched_group_barrier MFMA / 2 VALU interleave per step
 #endif
 
 typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));
@@ -1464,25 +1205,11 @@ drl_qnet_act_code4_kernel(QnetArgs a) {
                                                  (__attribute__((address_space(3))) void*)(wl + v0), 16, 0, 0);
             }
     };
-    // issue order: every tile's first code vector (the inputs of slices 0..5 at a 7x7 window), slices 0 and 1,
-    // the other code vectors, the other slices; slice t is readable once this wave's loads up to its DMAs have
-    // landed (in-order vmcnt) and every wave's (the barrier)
+    // issue order: slices 0 and 1, the codes, the other slices; slice t is readable once this wave's loads up to
+    // its DMAs have landed (in-order vmcnt) and every wave's (the barrier)
     constexpr int KE = KP < 2 ? KP : 2;
     uint32_t cw[TP][4 * NV];
     const int64_t gl0 = grp0 < gend ? grp0 : 0;
-#if DRL_QC4_EARLYVEC
-#pragma unroll
-    for (int h = 0; h < TP; ++h) load_vec(TP * gl0 + h, 0, cw[h]);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int t = 0; t < KE; ++t) dma(t);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int v = 1; v < NV; ++v)
-#pragma unroll
-        for (int h = 0; h < TP; ++h) load_vec(TP * gl0 + h, v, cw[h]);
-    constexpr int NE0 = 4 * (KP - KE) + TP * (NV - 1);  // vector ops younger than the slice-0 inputs
-#else
 #pragma unroll
     for (int t = 0; t < KE; ++t) dma(t);
     __builtin_amdgcn_sched_barrier(0);
@@ -1492,45 +1219,15 @@ drl_qnet_act_code4_kernel(QnetArgs a) {
     for (int h = 0; h < TP; ++h)
 #pragma unroll
         for (int i = 0; i < 4 * NV; ++i) asm volatile("s_waitcnt vmcnt(0)" : "+v"(cw[h][i]));
-    constexpr int NE0 = 4 * (KP - KE);
-#endif
+    constexpr int NE0 = 4 * (KP - KE);  // vector ops younger than the slice-0 inputs
     __builtin_amdgcn_sched_barrier(0);
-#if DRL_QC4_DMALOOP
-    // slices >= KE are staged inside the first pass's layer 0: slice s's four fragments at steps 1, 5, 9, 13 of
-    // slice s - 2 (one LDS-DMA instruction holds the issuing wave ~60-180 cycles: all 32 in the prologue kept
-    // every wave ~5k cycles from its first MFMA).  slice_ready(T) runs at step 16 T - PD, when slice T + 1's
-    // fragments issued at steps <= 16 - PD of slice T - 1 are younger than slice T's.
-    static_assert(!DRL_QC4_EARLYVEC && KE == 2, "DMALOOP stages slices >= 2 in the loop");
-    constexpr int NDY = (1 <= 16 - PD) + (5 <= 16 - PD) + (9 <= 16 - PD) + (13 <= 16 - PD);
-    if (grp0 >= gend) {  // a wave without a pass still stages its fragments
-#pragma unroll
-        for (int t = KE; t < KP; ++t) dma(t);
-    }
-#else
 #pragma unroll
     for (int t = KE; t < KP; ++t) dma(t);
-#endif
     __builtin_amdgcn_sched_barrier(0);
     uint32_t ncw[TP][4 * NV];  // the next pass's codes
-#if DRL_QC4_EARLYNEXT
-    // the second pass's codes, youngest of the prologue's loads (the slice waits below count them), in flight from
-    // the start: in the train loop they come from HBM, and a prefetch during the first pass's layer 1 left their
-    // latency exposed at the second pass's start (C5 act 42 us in the loop against 28 back to back).
-    // Unconditional (past the last pass the first pass's again, from L2), so every wait count is static.
-#pragma unroll
-    for (int h = 0; h < TP; ++h) load_codes(TP * (grp0 + gstride < gend ? grp0 + gstride : gl0) + h, ncw[h]);
-    constexpr int NNX = TP * NV;
-#else
-    constexpr int NNX = 0;
-#endif
-    __builtin_amdgcn_sched_barrier(0);
     auto slice_ready = [&](auto t_c) __attribute__((always_inline)) {
         constexpr int T = decltype(t_c)::value;
-#if DRL_QC4_DMALOOP
-        constexpr int N = T == 0 ? 0 : (T + 1 < KP ? NDY : 0);
-#else
-        constexpr int N = (T < KE ? NE0 : 4 * (KP - 1 - T)) + NNX;
-#endif
+        constexpr int N = T < KE ? NE0 : 4 * (KP - 1 - T);
         asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"i"(N) : "memory");
     };
     uint32_t mx = 0;  // bits of the largest activation split into fp16 (DRL_ERR_QNET_RANGE at >= 65520)
@@ -1565,14 +1262,7 @@ drl_qnet_act_code4_kernel(QnetArgs a) {
             }
         });
         // the exploration draw (independent of Q): rnd when u < epsilon, else -1
-        int explore;
-        {
-            const uint64_t ge = (uint64_t)(a.env_offset + env);
-            const uint64_t hsh = qn_splitmix64(a.seed ^ qn_splitmix64((a.step << 40) ^ (ge << 8) ^ 0xa5ull));
-            const float u = (float)(hsh >> 40) * (1.0f / 16777216.0f);
-            const int rnd = (int)(((hsh & 0xffffffffull) * (uint64_t)a.n_actions) >> 32);
-            explore = (u < qn_eps(a)) ? rnd : -1;
-        }
+        const int explore = explore_draw(a.seed, a.step, (uint64_t)(a.env_offset + env), a.n_actions, act_eps(a));
         uint4 f1[2][2][NT1];  // layer 1's fragments: [buffer][hi / lo][unit tile]
         uint4 f2h[KT2], f2l[KT2];  // the output layer's, and the biases
         f32x4 b1[KT2][2], bq;
@@ -1619,33 +1309,16 @@ drl_qnet_act_code4_kernel(QnetArgs a) {
                 __builtin_memcpy(&x, hl ? bl[t & 1][h] : bh[t & 1][h], 16);
                 acc[h][m] = MFMA_F16(w, x, (t == 0 && hl == 0) ? z4 : acc[h][m], 0, 0, 0);
             }
-#if DRL_QC4_DMALOOP
-            if constexpr (t + 2 < KP && (st == 1 || st == 5 || st == 9 || st == 13)) {  // slice t + 2's fragment
-                if (first) {  // (through the buffer resource: a uniform offset, no 64-bit lane address)
-                    constexpr int k = st / 4, h = k >> 1, u = k & 1;
-                    const int v0 = h * FLO + ((2 * wave + u) * KP + t + 2) * 64;
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(pbuf, (__attribute__((address_space(3))) void*)(wl + v0), 16,
-                                                             lane16, v0 * 16, 0, 0);
-                }
-            }
-#endif
             issue(std::integral_constant<int, S + PD>{});
-            if constexpr (t + 1 < KP) {  // dword st % 4 of tile st / 4 of the next slice's inputs, pinned to this
-                // step (empty asm on its input and outputs) so that it issues between this step's MFMAs
+            if constexpr (t + 1 < KP) {  // dword st % 4 of tile st / 4 of the next slice's inputs
                 constexpr int h = st / 4, dd = st % 4, D = 4 * (t + 1) + dd;
                 uint32_t w = cw[h][qc4_word<CPG, D>()];
-#if DRL_QC4_PIN
-                asm volatile("" : "+v"(w));
-#endif
 #ifdef DRL_DIAG_QC4_NODECODE  // timing diagnostic (wrong results): no channel decode in the loop
                 uint32_t xh = w;
 #else
                 uint32_t xh = qc4_bdword<CPG, D>(w, bias_group);
 #endif
                 uint32_t xl = qc4_as<uint32_t>(qc4_as<f16x2>(xh) * kLo2);
-#if DRL_QC4_PIN
-                asm volatile("" : "+v"(xh), "+v"(xl));
-#endif
                 bh[(t + 1) & 1][h][dd] = xh;
                 bl[(t + 1) & 1][h][dd] = xl;
             }
@@ -1653,18 +1326,9 @@ drl_qnet_act_code4_kernel(QnetArgs a) {
             // follow in layer 1, after ld1(1): waiting for f1[0] then waits for neither)
             if constexpr (t + 1 == KP && st == 3) ld1(0, 0);
             if constexpr (t + 1 == KP && st == 6) ld2(f2h, f2l, b1, bq);
-#if DRL_QC4_EARLYSPLIT
             // layer 1's first K-slice reads unit tiles 0 and 1, final after this slice's steps 8 and 9: tile
             // st - 11's split beside the last steps' MFMAs
             if constexpr (t + 1 == KP && st >= 11 && st - 11 < TP) split1_tile(0, 0, st - 11);
-#endif
-#if DRL_QC4_IGLP
-#pragma unroll
-            for (int i = 0; i < TP; ++i) {  // one MFMA, then two VALU, per MFMA of the step
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-            }
-#endif
 #ifdef DRL_QC_STAMPS
             if constexpr (st == SPS - 1) slice_ts[t] = (uint32_t)(__builtin_amdgcn_s_memtime() - ts0);
 #endif
@@ -1678,14 +1342,10 @@ drl_qnet_act_code4_kernel(QnetArgs a) {
         // ---- layer 1 (bias folded into layer 0); K-slice t's inputs split from layer 0's unit tiles 2t, 2t + 1,
         // the next slice's split beside this slice's MFMAs
         f32x4 bcc[TP][NT1], bcl[TP][NT1];
-#if !DRL_QC4_EARLYSPLIT
-        split1(0, 0);
-#endif
 #pragma unroll
         for (int t = 0; t < KT1; ++t) {
             if (t + 1 < KT1) ld1(t + 1, (t + 1) & 1);
-            if (t + 1 == KT1 && ngrp < gend && !(DRL_QC4_EARLYNEXT && grp == grp0)) {  // the next pass's codes (the
-                // first pass's successor was loaded in the prologue), into their own registers and younger than
+            if (t + 1 == KT1 && ngrp < gend) {  // the next pass's codes, into their own registers and younger than
                 // every layer-1 fragment (the compiler's wait counts for those then ignore them); copied at the end
 #pragma unroll
                 for (int h = 0; h < TP; ++h) load_codes(TP * ngrp + h, ncw[h]);
@@ -1702,15 +1362,6 @@ drl_qnet_act_code4_kernel(QnetArgs a) {
                 }
             }
             if (t + 1 < KT1) split1(t + 1, (t + 1) & 1);
-#if DRL_QC4_IGLP1
-            if (t + 1 < KT1) {  // the next slice's split interleaved with this slice's MFMAs: 1 MFMA, 3 VALU
-#pragma unroll
-                for (int i = 0; i < 3 * TP * NT1; ++i) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
-                }
-            }
-#endif
             __builtin_amdgcn_sched_barrier(0);
         }
 #ifdef DRL_QC_STAMPS
@@ -1762,19 +1413,9 @@ drl_qnet_act_code4_kernel(QnetArgs a) {
             q[i] = v;
         }
         if (env < a.E) {
-            int best = 0;
-            float bv = q[0];
-#pragma unroll
-            for (int i = 1; i < 8; ++i) {
-                const bool b = i < a.n_actions && q[i] > bv;
-                best = b ? i : best;
-                bv = b ? q[i] : bv;
-            }
-            a.actions[env * a.action_stride] = explore >= 0 ? explore : best;
-#ifndef DRL_QC_STAMPS
-            if (a.q)
+            store_act(a, env, explore, argmax_first(q, a.n_actions));
+            if (kStoreQ && a.q)  // (rolled, not store_q: the unrolled stores cost this kernel 2-7 more AGPRs)
                 for (int i = 0; i < a.n_actions; ++i) a.q[env * a.n_actions + i] = q[i];
-#endif
         }
 #ifdef DRL_QC_STAMPS
         __builtin_amdgcn_sched_barrier(0);
@@ -1797,25 +1438,9 @@ drl_qnet_act_code4_kernel(QnetArgs a) {
                 for (int i = 0; i < 4 * NV; ++i) cw[h][i] = ncw[h][i];
         }
     }
-    bool bad = mx >= 0x477ff000u;  // 65520.0f (NaN cannot reach a split: see split_f16)
-    bad |= lane == 0 && reinterpret_cast<const int32_t*>(a.packed + a.status_vec)[0] != 0;  // pack range flag
-    if (__ballot(bad) && lane == 0 && a.err) atomicOr(a.err, DRL_ERR_QNET_RANGE);
-    if (a.synth_n > 1) {  // as in drl_qnet_act_kernel (TP 16-env tiles per group)
-        const uint32_t nd = (uint32_t)a.synth_n - 1u;
-        const uint32_t per = (uint32_t)(TP * 16) * nd;
-        for (int64_t gg = grp0; gg < gend; gg += gstride) {
-            for (uint32_t k = (uint32_t)lane; k < per; k += 64u) {
-                const uint32_t el = k / nd;
-                const int64_t env = TP * 16 * gg + el;
-                const uint64_t drone = 1u + (k - el * nd);
-                if (env < a.E) {
-                    const uint64_t ctr = (a.synth_step << 40) ^ ((uint64_t)(a.env_offset + env) << 8) ^ drone;
-                    const uint64_t hh = qn_splitmix64(a.synth_seed ^ qn_splitmix64(ctr));
-                    a.actions[env * a.action_stride + (int64_t)drone] = (int32_t)(((hh >> 32) * 5ull) >> 32);
-                }
-            }
-        }
-    }
+    const bool bad = mx >= 0x477ff000u;  // 65520.0f (NaN cannot reach a split: see split_f16)
+    flag_qnet_range(a.err, a.packed + a.status_vec, bad, lane);
+    synth_tail<TP * 16>(a, grp0, gend, gstride, lane);
 }
 
 // ------------------------------------------------------------ add_many ---
@@ -1953,8 +1578,8 @@ hipError_t launch_qnet_act_code(const QnetArgs& a, int window, int num_cus, hipS
     if (nb2 > num_cus) nb2 = num_cus;
     const dim3 grid2((unsigned)nb2), block2(64 * QN_CODE2_WAVES);
 #define QN_CODE_LAUNCH(NT, W)                                                                                   \
-    if (a.lo0_lds) hipLaunchKernelGGL((drl_qnet_act_code_kernel<NT, true, W, 0>), grid, block, lds, s, a);     \
-    else hipLaunchKernelGGL((drl_qnet_act_code_kernel<NT, false, W, 0>), grid, block, lds, s, a)
+    if (a.lo0_lds) hipLaunchKernelGGL((drl_qnet_act_code_kernel<NT, true, W>), grid, block, lds, s, a);        \
+    else hipLaunchKernelGGL((drl_qnet_act_code_kernel<NT, false, W>), grid, block, lds, s, a)
     // DRL_QN_CODE=2: the two-tile kernel for the benchmark nets too (A/B knob, read per call so the parity
     // test can reach drl_qnet_act_code2_kernel: no packable net needs it at 32-bit code offsets)
     const char* v2e = getenv("DRL_QN_CODE");

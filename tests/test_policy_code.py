@@ -227,6 +227,58 @@ def test_qnet_act_code_exploration_and_synth(E, N, off):
     assert torch.equal(got[:, 1:], ref[:, 1:])
 
 
+_EPILOGUE_INPUTS = {}
+
+
+def _epilogue_inputs(E):
+    """(policy code, flat observation) of E envs after one step; built once per E and only read."""
+    if E not in _EPILOGUE_INPUTS:
+        env = _env(16, 3, 3, E, seed=9)
+        code = env.new_code()
+        _, _, obs = env.step(env.synth_actions(seed=2, step=0), obs_k=1, code=code)
+        _EPILOGUE_INPUTS[E] = (code, obs.reshape(E, -1).contiguous())
+    return _EPILOGUE_INPUTS[E]
+
+
+@gpu
+@pytest.mark.parametrize("N", [1, 3])
+@pytest.mark.parametrize("E", [31, 100])
+@pytest.mark.parametrize("kernel", ["bf16_obs", "f32_obs", "code_32_32", "code4", "code2"])
+def test_dense_act_epilogue_streams(kernel, E, N, monkeypatch):
+    """The epilogue of every dense act kernel, exactly: drone 0's action is the exploration stream's draw
+    (tests/test_dqn.py _hash_explore) where the env explores and the first argmax of the kernel's own Q row
+    elsewhere; the other columns are drl_synth_actions'; no error flag.  bf16_obs: drl_qnet_act_kernel;
+    f32_obs: drl_qnet_act_f32_kernel; code_32_32: drl_qnet_act_code_kernel; code4: drl_qnet_act_code4_kernel;
+    code2: drl_qnet_act_code2_kernel (DRL_QN_CODE=2).  E = 31: a full 16-env tile and a partial one; E = 100:
+    code4 (64 envs per wave pass) gets a second group with a partial and an empty tile, code2 (32 per pass) a
+    partial last pair; N = 1: no synthetic columns."""
+    from dronerl_amd import _native
+    from dronerl_amd.dqn import QNetwork
+    from tests.test_dqn import _hash_explore
+    code, x = _epilogue_inputs(E)
+    if kernel == "code2":
+        monkeypatch.setenv("DRL_QN_CODE", "2")
+    if kernel.endswith("_obs"):
+        net = QNetwork(x.shape[1], (128, 64), generator=torch.Generator().manual_seed(5), precision=kernel[:-4])
+        inp = x
+    else:
+        net, _ = _nets(x.shape[1], (32, 32) if kernel == "code_32_32" else (128, 64), seed=77)
+        inp = code
+    eps, seed, step, off = 0.3, 7, 3, 5000
+    acts = torch.full((E, N), -1, dtype=torch.int32, device="cuda")
+    q = torch.empty((E, 5), device="cuda")
+    net.act(inp, epsilon=eps, seed=seed, step=step, env_offset=off, actions=acts, q_out=q, synth=(2024, 9))
+    net.check_errors()
+    a, greedy = acts.cpu().numpy(), torch.argmax(q, dim=1).cpu().numpy()
+    for e in range(E):
+        explores, rnd = _hash_explore(seed, step, off + e, 5, eps)
+        assert a[e, 0] == (rnd if explores else greedy[e]), e
+    synth = torch.empty((E, N), dtype=torch.int32, device="cuda")
+    assert _native.lib().drl_synth_actions(2024, 9, off, E, N, synth.data_ptr(),
+                                           torch.cuda.current_stream().cuda_stream) == 0
+    assert np.array_equal(a[:, 1:], synth.cpu().numpy()[:, 1:])
+
+
 @gpu
 def test_qnet_code_input_checks():
     from dronerl_amd.dqn import QNetwork

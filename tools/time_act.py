@@ -24,7 +24,7 @@ def main():
     ap.add_argument("--stamps", action="store_true", help="library built with -DDRL_QC_STAMPS: phase cycles")
     ap.add_argument("--slices", type=int, default=0, help="v4 stamps: layer-0 slices per pass to print (10 at 7x7)")
     ap.add_argument("--group", type=int, default=64,
-                    help="envs per wave pass of the stamped code act (64: v4 kernel, 32: DRL_QN_CODE=2|3)")
+                    help="envs per wave pass of the stamped code act (64: v4 kernel, 32: DRL_QN_CODE=2)")
     ap.add_argument("--flush", action="store_true",
                     help="overwrite 256 MB between launches (cold L2/MALL, as after a step) and time each launch")
     ap.add_argument("--rewrite", action="store_true", help="with --flush: rewrite the input rows after the flush "
