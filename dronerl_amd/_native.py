@@ -43,8 +43,11 @@ EXPORTS = ["drl_abi_version", "drl_last_error", "drl_side_from_density", "drl_la
            "drl_step_code_replay_synth",
            # DQN learner (train_step / update_target / update_epsilon / sample)
            "drl_dqn_layout_query", "drl_dqn_init", "drl_dqn_train", "drl_dqn_train_fresh", "drl_dqn_sample_rows",
-           # conv Q-networks, the inference half (dronerl_amd.dqn.ConvQNetwork)
+           # conv Q-networks: pack and act (dronerl_amd.dqn.ConvQNetwork)
            "drl_convnet_packed_bytes", "drl_convnet_pack", "drl_convnet_act",
+           # the conv nets' DQN learner (dronerl_amd.dqn.ConvDQNLearner)
+           "drl_convnet_dqn_layout_query", "drl_convnet_dqn_init", "drl_convnet_dqn_train",
+           "drl_convnet_dqn_sample_rows",
            # measurement helper (the measured copy-kernel peak)
            "drl_hbm_probe"]
 

@@ -15,8 +15,12 @@ HASH = LIB + ".srchash"
 SOURCES = [os.path.join(CSRC, "dronerl_kernels.hip"), os.path.join(CSRC, "dronerl_api.cpp"),
            os.path.join(CSRC, "dronerl_env.cpp"), os.path.join(CSRC, "dronerl_qnet.hip"),
            os.path.join(CSRC, "dronerl_qnet_api.cpp"), os.path.join(CSRC, "dronerl_learn.hip"),
-           os.path.join(CSRC, "convnet", "dronerl_convnet.hip"), os.path.join(CSRC, "convnet", "dronerl_convnet_api.cpp")]
+           os.path.join(CSRC, "convnet", "dronerl_convnet.hip"), os.path.join(CSRC, "convnet", "dronerl_convnet_api.cpp"),
+           os.path.join(CSRC, "convlearn", "dronerl_convlearn.hip"),
+           os.path.join(CSRC, "convlearn", "dronerl_convlearn_api.cpp")]
 DEPS = SOURCES + [os.path.join(CSRC, "dronerl_internal.h"), os.path.join(CSRC, "dronerl_act_common.h"),
+                  os.path.join(CSRC, "dronerl_learn_common.h"),
+                  os.path.join(CSRC, "convlearn", "dronerl_convlearn_layout.h"),
                   os.path.join(CSRC, "convnet", "dronerl_convnet_layout.h"), os.path.join(REPO, "include", "dronerl.h")]
 ARCH = os.environ.get("DRL_OFFLOAD_ARCH", "gfx950")
 

@@ -16,8 +16,9 @@ reference module (same nn.Sequential names, so state dicts load unchanged)
 and its forward: dense nets flatten [B, H, W, C] row-major; conv nets permute
 to [B, C, H, W] first (dqn.py:80-81, 153-159).  `to_qnet` moves a dense net
 onto the MFMA consumer (dronerl_amd.dqn.QNetwork) when its widths allow;
-`save_dense` writes a (device-trained) dense net in the reference's three
-on-disk forms (jax save / save_as_torch, torch DQNAgent.save).
+`save_dense` / `save_conv` write a (device-trained) dense / conv net in the
+reference's three on-disk forms (jax save / save_as_torch, torch
+DQNAgent.save).
 """
 from __future__ import annotations
 
@@ -203,6 +204,78 @@ def save_dense(path: str, weights, biases, obs_shape, format: str = "torch", con
                 t[f"params.Dense_{i}.kernel"], t[f"params.Dense_{i}.bias"] = np.ascontiguousarray(w.T), b
             else:
                 t[f"network.dense_{i + 1}.weight"], t[f"network.dense_{i + 1}.bias"] = w, b
+    save_file(t, path, metadata=md)
+
+
+def save_conv(path: str, conv_weights, conv_biases, weights, biases, obs_shape, conv_layers, format: str = "torch",
+              hidden_layers=(16, 16), checkpoint_format_version: float = 0.1):
+    """Write a conv Q-network (conv_weights [out][in][kh][kw] / conv_biases,
+    then the dense tail weights [out][in] / biases with the Q head last; torch
+    layouts, any tensors or arrays) as the reference writes a trained agent:
+
+    * "torch": jax_impl/agents/dqn.py:305-357 save_as_torch: network.conv2d_{i}
+      .weight [out][in][kh][kw] / .bias and network.dense_{i}.weight [out][in]
+      / .bias (i from 1); metadata network_type "conv", dense_layers = the
+      dense widths after the convolutions (:314-315), conv_dense_layers,
+      conv_layers, obs_shape, action_shape, checkpoint_format "torch",
+      checkpoint_format_version;
+    * "jax": dqn.py:282-303 save: params.Conv_{i}.kernel [kh][kw][in][out]
+      (the torch weight transposed (2, 3, 1, 0)) / .bias and
+      params.Dense_{i}.kernel [in][out] / .bias (i from 0); the same keys with
+      checkpoint_format "jax", where dense_layers is the agent's
+      `hidden_layers` (a dense net's option, which train_jax.py carries along:
+      (16, 16) by default) and conv_dense_layers the widths in use;
+    * "torch_agent": torch_impl/agents/dqn.py:330-345 DQNAgent.save: the torch
+      names and only network_type, dense_layers, obs_shape, action_shape and
+      conv_layers with the keys out_channels, kernel_size, stride, padding.
+
+    conv_layers: the reference's tuple of dicts; the "torch" and "jax" forms
+    write str() of it as given (train_jax.py passes the command line's)."""
+    from safetensors.numpy import save_file
+    if format not in CHECKPOINT_FORMATS:
+        raise ValueError(f"format must be one of {CHECKPOINT_FORMATS}")
+    arr = lambda t: np.ascontiguousarray(np.asarray(t.detach().cpu() if torch.is_tensor(t) else t,  # noqa: E731
+                                                    dtype=np.float32))
+    cw, cb, ws, bs = ([arr(t) for t in ts] for ts in (conv_weights, conv_biases, weights, biases))
+    conv_layers = tuple(dict(c) for c in conv_layers)
+    if not cw or len(cw) != len(cb) or len(cw) != len(conv_layers):
+        raise ValueError("conv_weights, conv_biases and conv_layers: one entry per conv layer")
+    if not ws or len(ws) != len(bs) or any(w.ndim != 2 or b.shape != (w.shape[0],) for w, b in zip(ws, bs)):
+        raise ValueError("weights [out][in] and biases [out], one pair per dense layer")
+    obs_shape = tuple(int(v) for v in obs_shape)
+    side, cin = obs_shape[0], obs_shape[2]
+    one = lambda v: int(v[0] if isinstance(v, (tuple, list)) else v)  # noqa: E731
+    for i, (w, b, c) in enumerate(zip(cw, cb, conv_layers)):
+        k = one(c["kernel_size"])
+        if w.shape != (int(c["out_channels"]), cin, k, k) or b.shape != (w.shape[0],):
+            raise ValueError(f"conv layer {i}: weight {w.shape} does not match conv_layers / the previous layer")
+        side, cin = (side + 2 * one(c.get("padding", 0)) - k) // one(c.get("stride", 1)) + 1, w.shape[0]
+    if ws[0].shape[1] != side * side * cin or any(ws[i + 1].shape[1] != ws[i].shape[0] for i in range(len(ws) - 1)):
+        raise ValueError("dense widths do not chain from the flattened conv output")
+    dense = tuple(int(w.shape[0]) for w in ws[:-1])
+    md = {"network_type": "conv", "obs_shape": str(obs_shape), "action_shape": str((int(ws[-1].shape[0]),))}
+    t = {}
+    if format == "jax":
+        md.update({"dense_layers": str(tuple(hidden_layers)), "conv_layers": str(conv_layers),
+                   "conv_dense_layers": str(dense), "checkpoint_format": "jax",
+                   "checkpoint_format_version": str(checkpoint_format_version)})
+        for i, (w, b) in enumerate(zip(cw, cb)):
+            t[f"params.Conv_{i}.kernel"] = np.ascontiguousarray(np.transpose(w, (2, 3, 1, 0)))
+            t[f"params.Conv_{i}.bias"] = b
+        for i, (w, b) in enumerate(zip(ws, bs)):
+            t[f"params.Dense_{i}.kernel"], t[f"params.Dense_{i}.bias"] = np.ascontiguousarray(w.T), b
+    else:
+        if format == "torch":
+            md.update({"dense_layers": str(dense), "conv_dense_layers": str(dense), "conv_layers": str(conv_layers),
+                       "checkpoint_format": "torch", "checkpoint_format_version": str(checkpoint_format_version)})
+        else:
+            md.update({"dense_layers": str(dense), "conv_layers": str(tuple(
+                {"out_channels": c["out_channels"], "kernel_size": c["kernel_size"], "stride": c.get("stride", 1),
+                 "padding": c.get("padding", 0)} for c in conv_layers))})
+        for i, (w, b) in enumerate(zip(cw, cb)):
+            t[f"network.conv2d_{i + 1}.weight"], t[f"network.conv2d_{i + 1}.bias"] = w, b
+        for i, (w, b) in enumerate(zip(ws, bs)):
+            t[f"network.dense_{i + 1}.weight"], t[f"network.dense_{i + 1}.bias"] = w, b
     save_file(t, path, metadata=md)
 
 

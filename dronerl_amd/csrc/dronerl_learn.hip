@@ -37,6 +37,7 @@
 
 #include "dronerl_internal.h"
 #include "dronerl_act_common.h"
+#include "dronerl_learn_common.h"
 
 // every product and sum of this file rounds on its own (no FMA contraction): the order oracle/dqn_learner.py restates
 #pragma clang fp contract(off)
@@ -55,75 +56,15 @@ namespace drl {
 
 namespace {
 
-// buffers.py:79-90: B uniform indices in [0, current_size) (the reference draws
-// them with jax.random.randint; here a counter hash of (seed, step, row)).
-__device__ __forceinline__ int64_t dq_sample(uint64_t seed, int32_t step, int b, int64_t size) {
-    const uint64_t h = splitmix64(seed ^ splitmix64(((uint64_t)(uint32_t)step << 16) | (uint64_t)b));
-    return (int64_t)(((h >> 32) * (uint64_t)size) >> 32);
-}
-
-// Input k of replay row s: a policy-code row is decoded with the channel rules
-// of the observation writer (wrappers.py:10-31; drl_code_decode), an f32 row read.
-__device__ __forceinline__ float dq_input(const LearnArgs& a, const uint32_t* __restrict__ rows, int64_t s, int k) {
-    const uint32_t* row = rows + s * a.row_words;
-    if (a.code_w == 0) return __uint_as_float(row[k]);
-    const int cpg = lay::code_cpg(a.code_w), cpg8 = lay::code_cpg8(a.code_w);
-    const int cl = k / 6, ch = k - 6 * cl, grp = cl / cpg;
-    const uint32_t h = reinterpret_cast<const uint16_t*>(row)[grp * cpg8 + (cl - grp * cpg)];
-    const uint32_t obj = h & 7u, air = h >> 3;
-    switch (ch) {
-        case 0: return air ? 1.0f : 0.0f;
-        case 1: return (obj == OBJ_PACKET || (air & 0x80u)) ? 1.0f : 0.0f;
-        case 2: return obj == OBJ_DROPZONE ? 1.0f : 0.0f;
-        case 3: return obj == OBJ_STATION ? 1.0f : 0.0f;
-        case 4: return air ? (float)((int)(air & 0x7fu) - 1) / 100.0f : 0.0f;
-        default: return obj == OBJ_SKYSCRAPER ? 1.0f : 0.0f;
-    }
-}
-
-// optax.adam (scale_by_adam + scale(-lr)) + apply_updates, term by term:
-// mu = (1-b1) g + b1 mu; nu = (1-b2) g^2 + b2 nu; u = (mu / bc1) / (sqrt(nu / bc2)
-// + eps); p + u * (-lr).
-__device__ __forceinline__ float dq_adam(const LearnArgs& a, float p, float g, float* __restrict__ m,
-                                         float* __restrict__ v, float bc1, float bc2) {
-    const float mn = a.c1 * g + a.b1 * *m;
-    const float vn = a.c2 * (g * g) + a.b2 * *v;
-    *m = mn;
-    *v = vn;
-    const float u = (mn / bc1) / (__builtin_sqrtf(vn / bc2) + a.adam_eps);
-    return p + u * a.neg_lr;
-}
-
-// optax.incremental_update(new, old, tau) = tau * new + (1 - tau) * old
-__device__ __forceinline__ float dq_blend(const LearnArgs& a, float nw, float old) {
-    return a.tau * nw + a.one_minus_tau * old;
-}
+// (dq_sample, dq_input, dq_adam, dq_blend and the counters' arithmetic: dronerl_learn_common.h, shared with the
+// conv learner)
 
 // The counters at the end of a learner step (thread 0 of the online tail,
-// or of the one workgroup of a step without a sample): Adam's count and
-// powers, the loss, the epsilon decay, the step's plan (informative),
-// step + 1.  ctr: the values the kernel read at its start.
+// or of the one workgroup of a step without a sample).  ctr: the values the
+// kernel read at its start.
 __device__ void dq_finish(const LearnArgs& a, const DqnCounters& ctr, int trained, float loss, float bc1, float bc2) {
     if (threadIdx.x != 0) return;
-    DqnCounters* c = a.ctr;
-    const int32_t step = ctr.step;
-    if (trained) {
-        c->count = ctr.count + 1;
-        c->beta1_pow = ctr.beta1_pow * a.b1d;
-        c->beta2_pow = ctr.beta2_pow * a.b2d;
-    }
-    c->loss = trained ? loss : 0.0f;
-    float eps = ctr.epsilon;
-    if (step % a.eps_every == 0) {
-        const float d = eps * a.eps_decay;
-        eps = d > a.eps_end ? d : a.eps_end;  // jnp.maximum
-    }
-    c->epsilon = eps;
-    c->trained = trained;
-    c->target_due = step % a.target_every == 0 ? 1 : 0;
-    c->bc1 = bc1;
-    c->bc2 = bc2;
-    c->step = step + 1;
+    dq_finish_counters(a, a.ctr, ctr, trained, loss, bc1, bc2);
 }
 
 // Copy n words src(i) -> dst(i) with every thread holding DQN_STAGE loads in

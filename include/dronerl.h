@@ -588,8 +588,10 @@ int drl_dqn_sample_rows(const drl_qnet_desc* d, const drl_dqn_hparams* h, const 
                         int64_t* d_slots, hipStream_t stream);
 
 /* ------------------------------------------------------------------------
- * Convolutional Q-networks, the inference half (torch_impl/agents/dqn.py:85-159
- * ConvQNetwork, jax_impl/agents/dqn.py:66-94; sample_models/dqn-agent-5 is one):
+ * Convolutional Q-networks (torch_impl/agents/dqn.py:85-159 ConvQNetwork,
+ * jax_impl/agents/dqn.py:66-94; sample_models/dqn-agent-5 is one): inference
+ * (drl_convnet_pack, drl_convnet_act) and, below, the learner
+ * (drl_convnet_dqn_*):
  *   x: [E][W][W][6] f32 window (drl_obs's layout, channels last)
  *   per conv layer: y[oy][ox][co] = relu(b[co] + sum_{ky,kx,ci} w[co][ci][ky][kx]
  *       * x[oy*s + ky - p][ox*s + kx - p][ci]), x = 0 outside the map, output
@@ -597,8 +599,7 @@ int drl_dqn_sample_rows(const drl_qnet_desc* d, const drl_dqn_hparams* h, const 
  *   flatten in torch order (co*H*W + oy*W + ox; jax dqn.py:82 transposes to the
  *       same), 0..2 hidden Dense + ReLU, Dense(n_actions).
  * Numerics are DRL_QNET_F32's (fp16 hi/lo split operands, three MFMAs per
- * product tile): Q matches an f32 forward to f32 rounding.  Training conv
- * nets is not part of this ABI.
+ * product tile): Q matches an f32 forward to f32 rounding.
  * Limits (each refused by name when the description is validated, by every
  * call below): window odd in [3, 9]; 1..3 conv layers with out_channels in
  * [1, 32], square kernel_size in [1, 5], stride in [1, 3], padding in [0, 4],
@@ -649,6 +650,65 @@ int drl_convnet_act(const drl_convnet_desc* d, const void* d_packed, const void*
                     int64_t obs_stride, float epsilon, const float* d_epsilon, uint64_t seed, uint64_t step,
                     int64_t env_offset, int32_t* d_actions, int64_t action_stride, float* d_q, int32_t* d_err,
                     hipStream_t stream);
+
+/* ------------------------------------------------------------------------
+ * DQN learner for conv nets: one drl_convnet_dqn_train call is the learner
+ * block of one train_jax.py scan step (:68-98) with network_type == 'conv',
+ * with exactly the semantics written above drl_dqn_train (sample when size >=
+ * batch, q = Q(obs)[action], td = reward + gamma * max_a Q_target(next_obs) *
+ * (1 - done), loss = mean((q - td)^2), its gradient with respect to every conv
+ * and dense parameter, optax.adam, the target blend every
+ * target_update_interval steps, the epsilon decay every epsilon_decay_every
+ * steps, step += 1; with size < batch nothing trains and only the schedule
+ * advances).  The same drl_dqn_hparams, drl_dqn_counters, drl_replay and row
+ * draw (the counter hash of (sample_seed, step, row)).  relu'(0) = 0.
+ * The call is a fixed sequence of stream-ordered launches (rows: one
+ * workgroup per sampled row, forward and backward to every layer's deltas;
+ * update: one thread per dense parameter and one wave per conv parameter,
+ * the gradient summed in a fixed order, Adam, the target blend; counters; the
+ * pack kernel on the online set): no workgroup waits for another, no float atomics, so the
+ * result is reproducible bit for bit; it allocates nothing, does not
+ * synchronise and can be captured into a graph, whose replays continue the
+ * schedule.  Numerics: f32, each product and sum rounded on its own.
+ * Limits: drl_convnet_desc's, batch in [1, 64], and one row's input,
+ * activations and deltas of every layer (4 bytes each, each layer's rounded
+ * up to 16 bytes) within DRL_CONVNET_DQN_ROW_BYTES_MAX, the LDS one workgroup
+ * of the rows kernel takes; a larger net is refused by name.
+ * ------------------------------------------------------------------------ */
+#define DRL_CONVNET_DQN_MAX_LAYERS 6 /* DRL_CONVNET_MAX_CONV + DRL_CONVNET_MAX_DENSE + the Q head */
+#define DRL_CONVNET_DQN_ROW_BYTES_MAX 65536
+/* The agent block (device, caller-owned, one allocation of `bytes`, 16-B
+ * aligned): four parameter sets (online, target, Adam mu, Adam nu) of n_params
+ * floats each -- layer l's weight at weight_off[l], its bias at bias_off[l]
+ * (floats from the set's start); the conv layers first ([out][in][k][k]), then
+ * the dense layers ([out][in], the first one's columns in torch's flatten
+ * order, the Q head last): torch layouts --, one drl_dqn_counters at
+ * counters_off, and the learner's scratch. */
+typedef struct drl_convnet_dqn_layout {
+    int64_t n_params;
+    int32_t n_layers, row_bytes;  /* layers; the per-row working set (informative) */
+    int64_t weight_off[DRL_CONVNET_DQN_MAX_LAYERS], bias_off[DRL_CONVNET_DQN_MAX_LAYERS];
+    int64_t online_off, target_off, m_off, v_off;  /* bytes */
+    int64_t counters_off, scratch_off, bytes;       /* bytes */
+} drl_convnet_dqn_layout;
+
+/* Host only (works without a device). */
+int drl_convnet_dqn_layout_query(const drl_convnet_desc* d, int32_t batch, drl_convnet_dqn_layout* layout);
+/* Zero the Adam moments, the counters and the scratch, epsilon = epsilon_start.
+ * The caller writes the online and target parameters.  Does not synchronise. */
+int drl_convnet_dqn_init(const drl_convnet_desc* d, int32_t batch, void* d_agent, float epsilon_start,
+                         hipStream_t stream);
+/* One learner step on replay `r` holding `size` transitions (0 <= size <=
+ * capacity).  The replay's rows: f32 observations (obs_floats >= W*W*6) for a
+ * DRL_QNET_INPUT_OBS description, policy code rows (drl_policy_code_bytes / 4
+ * words) for a DRL_QNET_INPUT_CODE one.  d_packed: the online net's packed
+ * image; after the call it is byte for byte drl_convnet_pack of the online
+ * set (a weight outside the fp16 split range raises its status word). */
+int drl_convnet_dqn_train(const drl_convnet_desc* d, const drl_dqn_hparams* h, void* d_agent, void* d_packed,
+                          const struct drl_replay* r, int64_t size, hipStream_t stream);
+/* drl_dqn_sample_rows for this agent block. */
+int drl_convnet_dqn_sample_rows(const drl_convnet_desc* d, const drl_dqn_hparams* h, const void* d_agent,
+                                int64_t size, int64_t* d_slots, hipStream_t stream);
 
 #ifdef __cplusplus
 }
