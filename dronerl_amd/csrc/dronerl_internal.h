@@ -520,6 +520,11 @@ constexpr uint32_t DQN_SPIN_WORD = 1u << 24, DQN_SPIN_GRANULE = 1u << 22;
 // once on this device with `lds` bytes of dynamic LDS each (occupancy x compute units)
 int dqn_train_resident_capacity(size_t lds, int num_cus);
 
+// (dronerl_qnet_api.cpp) validate a description and lay its packed net out: 0, or -1 with drl_last_error set;
+// the pack launch's arguments for that layout (w, b: one pointer per layer)
+__attribute__((visibility("hidden"))) int qnet_layout_of(const drl_qnet_desc* d, QnetLayout* L);
+__attribute__((visibility("hidden"))) void qnet_pack_args(const QnetLayout& L, void* d_packed, const float* const* w,
+                                                          const float* const* b, QnetPack* p);
 hipError_t launch_qnet_pack(const QnetPack& p, hipStream_t s);
 hipError_t launch_dqn_train(const LearnArgs& a, size_t lds_grad, hipStream_t s);
 hipError_t launch_dqn_init(void* counters, float epsilon, hipStream_t s);

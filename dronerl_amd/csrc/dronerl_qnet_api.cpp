@@ -782,3 +782,12 @@ int drl_dqn_train_fresh(const drl_qnet_desc* d, const drl_dqn_hparams* h, void* 
 }
 
 }  // extern "C"
+
+// The description check and the pack launch's arguments for the other dense learner's host API
+// (largelearn/dronerl_largelearn_api.cpp): one rule for what a drl_qnet_desc may hold, one packed layout.
+namespace drl {
+int qnet_layout_of(const drl_qnet_desc* d, QnetLayout* L) { return qnet_layout(d, L); }
+void qnet_pack_args(const QnetLayout& L, void* d_packed, const float* const* w, const float* const* b, QnetPack* p) {
+    fill_pack(L, d_packed, w, b, p);
+}
+}  // namespace drl

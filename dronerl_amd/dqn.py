@@ -90,6 +90,10 @@ def _bind(L):
         "drl_dqn_train_fresh": [D, ctypes.POINTER(DrlDqnHParams), _vp, _vp, ctypes.POINTER(DrlReplay), i64,
                                 ctypes.POINTER(DrlReplayBatch), _vp],
         "drl_dqn_sample_rows": [D, ctypes.POINTER(DrlDqnHParams), _vp, i64, _vp, _vp],
+        "drl_dqn_large_layout_query": [D, i32, ctypes.POINTER(DrlDqnLayout)],
+        "drl_dqn_large_init": [D, i32, _vp, f32, _vp],
+        "drl_dqn_large_train": [D, ctypes.POINTER(DrlDqnHParams), _vp, _vp, ctypes.POINTER(DrlReplay), i64, _vp],
+        "drl_dqn_large_sample_rows": [D, ctypes.POINTER(DrlDqnHParams), _vp, i64, _vp, _vp],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -858,6 +862,102 @@ class DQNLearner:
         d = self.block[self.layout.counters_off + 16:self.layout.counters_off + 32].view(torch.float64).cpu()
         return {"step": int(i[0]), "count": int(i[1]), "epsilon": float(f[2]), "loss": float(f[3]),
                 "beta1_pow": float(d[0]), "beta2_pow": float(d[1])}
+
+
+DQN_MAX_BATCH, DQN_LARGE_MAX_BATCH = 64, 4096  # drl_dqn_train's batch limit; DRL_DQN_LARGE_MAX_BATCH
+
+
+class LargeBatchDQNLearner(DQNLearner):
+    """DQNLearner for replay batches up to 4096 (train_jax.py --batch_size
+    beyond the single-launch learner's 64): the same agent block layout for
+    the four parameter sets and the counters, the same semantics and the same
+    arithmetic bit for bit (oracle/dqn_learner.py's order; at batch <= 64 both
+    learners leave identical sets, counters and packed image), run as a fixed
+    chain of stream-ordered launches (drl_dqn_large_train: rows, each layer's
+    forward, TD, each layer's backward, update, counters, re-pack) with no
+    synchronisation and no wait between workgroups, so `train` is
+    graph-capturable.  The surface is DQNLearner's without `train(fresh=)`."""
+
+    def __init__(self, net: QNetwork, hp: Optional[DQNHParams] = None, target=None,
+                 generator: Optional[torch.Generator] = None):
+        self.net, self.hp = net, hp or DQNHParams()
+        self.L = _bind(net.L)
+        lay = DrlDqnLayout()
+        if self.L.drl_dqn_large_layout_query(ctypes.byref(net.desc), self.hp.batch, ctypes.byref(lay)):
+            raise ValueError(self.L.drl_last_error().decode())
+        self.layout = lay
+        dev = net.device
+        self.block = torch.zeros(lay.bytes, dtype=torch.uint8, device=dev)
+        n = lay.n_params
+        self.sets = {k: self.block[getattr(lay, k + "_off"):getattr(lay, k + "_off") + 4 * n].view(torch.float32)
+                     for k in ("online", "target", "m", "v")}
+        ctr = self.block[lay.counters_off:lay.counters_off + 64]
+        self._ctr_f = ctr.view(torch.float32)
+        self._ctr_i = ctr.view(torch.int32)
+        self.epsilon = self._ctr_f[2:3]  # drl_dqn_counters.epsilon
+        shapes = [(w.shape, b.shape) for w, b in zip(net.weights, net.biases)]
+        if target is None:  # (DQNLearner's default: the reference's own key, dqn.py:119-121)
+            g = generator if generator is not None else torch.Generator().manual_seed(1)
+            tw = [flax_kernel_init(ws, 2.0 if l < len(shapes) - 1 else 1.0, g) for l, (ws, _) in enumerate(shapes)]
+            target = (tw, [torch.zeros(bs) for _, bs in shapes])
+        for l, ((w, b), (tw_, tb_)) in enumerate(zip(self.params("online"), self.params("target"))):
+            w.copy_(net.weights[l])
+            b.copy_(net.biases[l])
+            tw_.copy_(target[0][l].to(dev, torch.float32))
+            tb_.copy_(target[1][l].to(dev, torch.float32))
+        online = self.params("online")
+        net.weights = [w for w, _ in online]  # the net now reads the live parameters
+        net.biases = [b for _, b in online]
+        net.pack()
+        self._hp = self.hp.c()
+        self.restart()
+
+    def train(self, rb: "ReplayBuffer"):
+        """One learner block (train_jax.py:68-98) on the replay's current
+        contents (rb.size transitions): f32 rows for an "obs" net, policy-code
+        rows for a "code" one."""
+        if rb.obs.device != self.block.device:
+            raise ValueError("the replay buffer must be on the learner's device")
+        _check(self.L, self.L.drl_dqn_large_train(ctypes.byref(self.net.desc), ctypes.byref(self._hp),
+                                                  _vp(self.block.data_ptr()), _vp(self.net.packed.data_ptr()),
+                                                  ctypes.byref(rb._c), rb.size, _stream(self.block.device)))
+
+    def sample_slots(self, size: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The replay slots (int64 [batch], in [0, size)) the next train()
+        draws (drl_dqn_large_sample_rows; stream-ordered, no sync)."""
+        if out is None:
+            out = torch.empty(self.hp.batch, dtype=torch.int64, device=self.block.device)
+        _on(out, self.block.device, torch.int64, "out")
+        if out.numel() != self.hp.batch or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous int64 [{self.hp.batch}] tensor")
+        _check(self.L, self.L.drl_dqn_large_sample_rows(ctypes.byref(self.net.desc), ctypes.byref(self._hp),
+                                                        _vp(self.block.data_ptr()), int(size), _vp(out.data_ptr()),
+                                                        _stream(self.block.device)))
+        return out
+
+    def check_errors(self):
+        """Synchronise and raise if the refreshed act image holds a weight
+        outside the fp16 split range (the learner's launches wait for nothing,
+        so there is no timeout to report)."""
+        if self.net.precision == "f32" and int(self.net.packed[-4].item()):
+            raise DroneRLError("drl_dqn_large_train: a learned weight left the f32 act's range (|w| >= 65504 or "
+                               "not finite); the act's Q values are not valid")
+
+    def restart(self, epsilon: Optional[float] = None):
+        """drl_dqn_large_init on the current parameters: Adam's moments and
+        the counters from zero (step 0, epsilon `epsilon` or
+        hp.epsilon_start).  The online and target parameters are kept."""
+        eps = self.hp.epsilon_start if epsilon is None else float(epsilon)
+        _check(self.L, self.L.drl_dqn_large_init(ctypes.byref(self.net.desc), self.hp.batch,
+                                                 _vp(self.block.data_ptr()), eps, _stream(self.block.device)))
+
+
+def make_learner(net: QNetwork, hp: Optional[DQNHParams] = None, **kw):
+    """The dense nets' learner for hp.batch: DQNLearner (one launch, batches up
+    to 64) or LargeBatchDQNLearner (a launch chain, batches up to 4096)."""
+    hp = hp or DQNHParams()
+    cls = DQNLearner if hp.batch <= DQN_MAX_BATCH else LargeBatchDQNLearner
+    return cls(net, hp, **kw)
 
 
 class ConvDQNLearner:

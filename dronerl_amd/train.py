@@ -46,6 +46,9 @@ def train(params: EnvParams, num_envs: int, num_steps: int, hidden: Sequence[int
     dqn.DQNHParams (default: train_jax.py's defaults with num_steps, so
     epsilon decays as :133-134 schedules it).  hidden: 1-3 widths, each a
     multiple of 8 in [8, 128] (train_jax.py's default net is (16, 16)).
+    hp.batch (--batch_size): 1..4096 for dense nets (dqn.make_learner: the
+    single-launch learner up to 64, the large-batch one above), 1..64 for
+    conv nets.
 
     network_type "conv" (train_jax.py --network_type conv): a ConvQNetwork
     of conv_layers (the reference's tuple of dicts; default train_jax.py's
@@ -59,7 +62,7 @@ def train(params: EnvParams, num_envs: int, num_steps: int, hidden: Sequence[int
     replay ring is sharded (global_learner.ShardedReplay) and every rank runs
     the same learner; env_offset is then ignored.  The returned rate counts
     every rank's envs."""
-    from .dqn import ConvDQNLearner, ConvQNetwork, DQNHParams, DQNLearner, QNetwork, ReplayBuffer
+    from .dqn import ConvDQNLearner, ConvQNetwork, DQNHParams, QNetwork, ReplayBuffer, make_learner
     from .distributed import shard_envs
     from .env import BatchedDeliveryDrones
     from .global_learner import ShardedReplay
@@ -86,7 +89,8 @@ def train(params: EnvParams, num_envs: int, num_steps: int, hidden: Sequence[int
         learner = ConvDQNLearner(net, hp, generator=torch.Generator().manual_seed(seed + 1))
     else:
         net = QNetwork(D, tuple(hidden), device=dev, generator=torch.Generator().manual_seed(seed), input="code")
-        learner = DQNLearner(net, hp, generator=torch.Generator().manual_seed(seed + 1))
+        # (batches up to 64: DQNLearner's one launch; up to 4096: LargeBatchDQNLearner's launch chain)
+        learner = make_learner(net, hp, generator=torch.Generator().manual_seed(seed + 1))
     if shard:
         rb = ShardedReplay(memory_size, D, dev, num_envs, shard.env_offset, shard.num_envs, rank, world,
                            code_radius=r, group=group)

@@ -501,7 +501,8 @@ int drl_qnet_act_eps(const drl_qnet_desc* d, const void* d_packed, const void* d
  * Dense nets of drl_qnet_desc (1-3 hidden layers, <= 128 wide, <= 8 actions).
  * ------------------------------------------------------------------------ */
 typedef struct drl_dqn_hparams {
-    int32_t batch;                  /* sample batch, 1..64 (train_jax.py --batch_size, 8) */
+    int32_t batch;                  /* sample batch (train_jax.py --batch_size, 8): 1..64 for drl_dqn_train and
+                                       drl_convnet_dqn_train, 1..DRL_DQN_LARGE_MAX_BATCH for drl_dqn_large_train */
     int32_t target_update_interval; /* >= 1 (--target_update_interval, 10) */
     int32_t epsilon_decay_every;    /* >= 1 (--epsilon_decay_every, 5) */
     int32_t reserved;               /* 0 */
@@ -586,6 +587,43 @@ int drl_dqn_train_fresh(const drl_qnet_desc* d, const drl_dqn_hparams* h, void* 
  * one global ring, train_jax.py:196-212). */
 int drl_dqn_sample_rows(const drl_qnet_desc* d, const drl_dqn_hparams* h, const void* d_agent, int64_t size,
                         int64_t* d_slots, hipStream_t stream);
+
+/* ------------------------------------------------------------------------
+ * The same learner for replay batches up to DRL_DQN_LARGE_MAX_BATCH: one
+ * drl_dqn_large_train call is the learner block written above drl_dqn_train,
+ * with its semantics and its arithmetic bit for bit (the rows of a step are
+ * the same counter hash's, so at batch <= 64 both calls leave the same
+ * parameter sets, counters and packed image).  Where drl_dqn_train is one
+ * launch whose workgroups hand a batch of <= 64 rows to each other through
+ * LDS, this is a fixed chain of stream-ordered launches on `stream` (the rows,
+ * each layer's forward of both nets, the TD error, each layer's backward, the
+ * parameter update, the counters, the re-pack): no workgroup waits for
+ * another, nothing needs to be co-resident, no float atomic is used, nothing
+ * is allocated and nothing synchronises, so the call is graph-capturable and
+ * a replayed graph continues the schedule.  With size < batch only the target
+ * blend (when due) and the counters run.  The same drl_dqn_hparams,
+ * drl_dqn_counters, drl_replay and row kinds (f32 rows for a
+ * DRL_QNET_INPUT_OBS net, policy-code rows for a DRL_QNET_INPUT_CODE one);
+ * dense nets of drl_qnet_desc.  Every argument is validated before any device
+ * work.
+ * ------------------------------------------------------------------------ */
+#define DRL_DQN_LARGE_MAX_BATCH 4096
+/* Host only.  drl_dqn_layout with drl_dqn_layout_query's parameter-set offsets
+ * (n_params, weight_off, bias_off, online_off .. counters_off) and a scratch
+ * sized for `batch` (the rows' decoded inputs, both nets' activations, the
+ * deltas); grad_workgroups = grad_lds_bytes = 0. */
+int drl_dqn_large_layout_query(const drl_qnet_desc* d, int32_t batch, drl_dqn_layout* layout);
+/* drl_dqn_init for this agent block: the Adam moments and the counters from
+ * zero, epsilon = epsilon_start; the caller writes the online and target
+ * parameters.  Stream-ordered: it does not synchronise. */
+int drl_dqn_large_init(const drl_qnet_desc* d, int32_t batch, void* d_agent, float epsilon_start, hipStream_t stream);
+/* One learner step (drl_dqn_train's arguments).  After the call d_packed is
+ * byte for byte drl_qnet_pack of the online set. */
+int drl_dqn_large_train(const drl_qnet_desc* d, const drl_dqn_hparams* h, void* d_agent, void* d_packed,
+                        const struct drl_replay* r, int64_t size, hipStream_t stream);
+/* drl_dqn_sample_rows for this agent block: h->batch slots. */
+int drl_dqn_large_sample_rows(const drl_qnet_desc* d, const drl_dqn_hparams* h, const void* d_agent, int64_t size,
+                              int64_t* d_slots, hipStream_t stream);
 
 /* ------------------------------------------------------------------------
  * Convolutional Q-networks (torch_impl/agents/dqn.py:85-159 ConvQNetwork,
