@@ -14,7 +14,7 @@ from .constants import Action, Object
 from .params import EnvParams, side_from_density
 
 __all__ = ["Action", "Object", "EnvParams", "side_from_density", "BatchedDeliveryDrones", "DroneEnvState",
-           "QNetwork", "ConvQNetwork"]
+           "QNetwork", "ConvQNetwork", "WideQNetwork"]
 
 
 def __getattr__(name):
@@ -22,7 +22,7 @@ def __getattr__(name):
     if name in ("BatchedDeliveryDrones", "DroneEnvState"):
         from . import env
         return getattr(env, name)
-    if name in ("QNetwork", "ConvQNetwork"):  # the on-device Q-networks (dense; conv: inference only)
+    if name in ("QNetwork", "ConvQNetwork", "WideQNetwork"):  # the on-device Q-networks
         from . import dqn
         return getattr(dqn, name)
     raise AttributeError(name)

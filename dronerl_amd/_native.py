@@ -50,6 +50,9 @@ EXPORTS = ["drl_abi_version", "drl_last_error", "drl_side_from_density", "drl_la
            "drl_convnet_dqn_sample_rows",
            # the dense nets' learner at batches up to 4096 (dronerl_amd.dqn.LargeBatchDQNLearner)
            "drl_dqn_large_layout_query", "drl_dqn_large_init", "drl_dqn_large_train", "drl_dqn_large_sample_rows",
+           # dense nets with hidden widths up to 256 (dronerl_amd.dqn.WideQNetwork, WideDQNLearner)
+           "drl_widenet_packed_bytes", "drl_widenet_pack", "drl_widenet_act", "drl_widenet_dqn_layout_query",
+           "drl_widenet_dqn_init", "drl_widenet_dqn_train", "drl_widenet_dqn_sample_rows",
            # measurement helper (the measured copy-kernel peak)
            "drl_hbm_probe"]
 

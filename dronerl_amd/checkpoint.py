@@ -282,11 +282,12 @@ def save_conv(path: str, conv_weights, conv_biases, weights, biases, obs_shape, 
 def to_qnet(ck: Checkpoint, device=None, input: str = "obs"):
     """A checkpoint on the MFMA consumer: a dense one as
     dronerl_amd.dqn.QNetwork (hidden widths multiples of 8 in [8, 128], 1-3
-    layers: the reference's default (16, 16) net among them), a conv one
+    layers: the reference's default (16, 16) net among them) or, with a width
+    in (128, 256], as dronerl_amd.dqn.WideQNetwork (qnet_class_of), a conv one
     (torch or jax format: read_checkpoint yields torch layouts for both) as
     dronerl_amd.dqn.ConvQNetwork (its limits: include/dronerl.h
     drl_convnet_desc).  input "code": the net acts from the policy code."""
-    from .dqn import ConvQNetwork, QNetwork
+    from .dqn import ConvQNetwork, WideQNetwork
     if ck.network_type == "conv":
         if any(w % 8 or not 8 <= w <= 128 for w in ck.dense_layers):
             raise ValueError(f"dense widths {ck.dense_layers} unsupported by drl_convnet (multiples of 8 in [8, 128])")
@@ -299,13 +300,28 @@ def to_qnet(ck: Checkpoint, device=None, input: str = "obs"):
                  [t(f"network.dense_{i + 1}.weight") for i in range(nd)],
                  [t(f"network.dense_{i + 1}.bias") for i in range(nd)])
         return net
-    if input != "obs":
-        raise ValueError("input='code' for a dense checkpoint: build a QNetwork(input='code') and load it")
-    if not ck.dense_layers or len(ck.dense_layers) > 3 or any(w % 8 or not 8 <= w <= 128 for w in ck.dense_layers):
-        raise ValueError(f"hidden widths {ck.dense_layers} unsupported by drl_qnet (multiples of 8 in [8, 128])")
+    cls = qnet_class_of(ck.dense_layers)
+    if cls is WideQNetwork:
+        net = cls(int(np.prod(ck.obs_shape)), ck.dense_layers, int(ck.action_shape[0]), device=device, input=input)
+    else:
+        if input != "obs":
+            raise ValueError("input='code' for a dense checkpoint: build a QNetwork(input='code') and load it")
+        net = cls(int(np.prod(ck.obs_shape)), ck.dense_layers, int(ck.action_shape[0]), device=device)
     n = len(ck.dense_layers) + 1
-    net = QNetwork(int(np.prod(ck.obs_shape)), ck.dense_layers, int(ck.action_shape[0]), device=device)
     ws = [torch.from_numpy(np.array(ck.tensors[f"network.dense_{i + 1}.weight"])) for i in range(n)]
     bs = [torch.from_numpy(np.array(ck.tensors[f"network.dense_{i + 1}.bias"])) for i in range(n)]
     net.load(ws, bs)
     return net
+
+
+def qnet_class_of(dense_layers):
+    """The device class of a dense net's hidden widths (1-3 multiples of 8):
+    dronerl_amd.dqn.QNetwork when every width is at most 128, WideQNetwork when
+    one is in (128, 256] (the reference sweep's (256, 128, 64) agent);
+    anything else is refused."""
+    from . import dqn
+    widths = tuple(int(w) for w in dense_layers)
+    if not widths or len(widths) > 3 or any(w % 8 or not 8 <= w <= dqn.WIDENET_MAX_WIDTH for w in widths):
+        raise ValueError(f"hidden widths {widths} unsupported by drl_qnet / drl_widenet (1-3 multiples of 8 in "
+                         f"[8, {dqn.WIDENET_MAX_WIDTH}])")
+    return dqn.WideQNetwork if dqn.is_wide(widths) else dqn.QNetwork

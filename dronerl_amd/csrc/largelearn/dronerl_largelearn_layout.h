@@ -55,14 +55,17 @@ struct Plan {
 };
 
 // Lay the agent block out for a dense net of n_layers layers (in[l] -> out[l]; a policy-code net: code_w = its
-// window) and a batch.  Returns nullptr, or the message for drl_last_error.
-inline const char* plan(int n_layers, const int32_t* in, const int32_t* out, int code_w, int32_t batch, Plan* P) {
+// window) and a batch.  max_width: the hidden widths' limit (drl_qnet_desc's by default; the wide nets' API,
+// widenet/, passes its own: no kernel of the chain depends on it).  Returns nullptr, or the message for
+// drl_last_error.
+inline const char* plan(int n_layers, const int32_t* in, const int32_t* out, int code_w, int32_t batch, Plan* P,
+                        int max_width = kMaxWidth) {
     if (!in || !out || !P) return "internal: the large-batch plan's arguments are NULL";
     if (batch < 1 || batch > kMaxBatch) return "batch must be in [1, 4096] (DRL_DQN_LARGE_MAX_BATCH)";
     if (n_layers < 2 || n_layers > kMaxLayers) return "n_hidden must be 1, 2 or 3";
     for (int l = 0; l < n_layers; ++l) {
-        if (in[l] < 1 || in[l] > (l == 0 ? kMaxIn : kMaxWidth) || out[l] < 1 ||
-            out[l] > (l + 1 < n_layers ? kMaxWidth : kMaxActions) || (l > 0 && in[l] != out[l - 1]))
+        if (in[l] < 1 || in[l] > (l == 0 ? kMaxIn : max_width) || out[l] < 1 ||
+            out[l] > (l + 1 < n_layers ? max_width : kMaxActions) || (l > 0 && in[l] != out[l - 1]))
             return "internal: layer sizes outside drl_qnet_desc's limits";
         if (l + 1 < n_layers && out[l] % 4) return "hidden widths must be multiples of 8 in [8, 128]";
     }

@@ -1,0 +1,247 @@
+// dronerl_widenet_api.cpp — C ABI of the wide dense Q-networks (include/dronerl.h drl_widenet_*; kernels in
+// dronerl_widenet.hip, layout in dronerl_widenet_layout.h).  The learner calls run the large-batch learner's
+// launch chain (largelearn/) on a plan with this family's width limit, then the wide pack kernel.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <mutex>
+#include <vector>
+
+#include "../../../include/dronerl.h"
+#include "../dronerl_internal.h"
+#include "../largelearn/dronerl_largelearn_layout.h"
+#include "dronerl_widenet_layout.h"
+
+extern "C" __attribute__((visibility("hidden"))) int drl_internal_fail(const char* msg);
+
+namespace {
+
+int fail(const char* m) { return drl_internal_fail(m); }
+
+int hip_fail(int e, const char* what) {
+    char buf[256];
+    snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString((hipError_t)e));
+    return fail(buf);
+}
+
+// Every limit is checked here, by every call: nothing is refused at launch.
+int wn_layout(const drl_widenet_desc* d, drl::wn::Layout* L) {
+    const char* msg = drl::wn::layout(d, L);
+    return msg ? fail(msg) : 0;
+}
+
+// ... and the learner's plan for that net at `batch`
+int wn_plan(const drl_widenet_desc* d, int32_t batch, drl::wn::Layout* L, drl::ll::Plan* P) {
+    if (wn_layout(d, L)) return -1;
+    int32_t in[drl::wn::kMaxLayers], out[drl::wn::kMaxLayers];
+    for (int l = 0; l < L->n_layers; ++l) {
+        in[l] = L->l[l].in;
+        out[l] = L->l[l].out;
+    }
+    const char* msg = drl::ll::plan(L->n_layers, in, out, L->code_w, batch, P, drl::wn::kMaxWidth);
+    return msg ? fail(msg) : 0;
+}
+
+int num_cus() {
+    static std::mutex mu;
+    static std::vector<int> cache;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 256;
+    std::lock_guard<std::mutex> g(mu);
+    if ((int)cache.size() <= dev) cache.resize(dev + 1, 0);
+    if (!cache[dev]) {
+        int n = 0;
+        cache[dev] = hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0 ? n : 256;
+    }
+    return cache[dev];
+}
+
+}  // namespace
+
+extern "C" {
+
+int drl_widenet_packed_bytes(const drl_widenet_desc* d, int64_t* bytes) {
+    drl::wn::Layout L;
+    if (wn_layout(d, &L)) return -1;
+    if (!bytes) return fail("bytes is NULL");
+    *bytes = (int64_t)L.total_words * 4;
+    return 0;
+}
+
+int drl_widenet_pack(const drl_widenet_desc* d, const float* const* d_weights, const float* const* d_biases,
+                     void* d_packed, hipStream_t stream) {
+    drl::wn::PackArgs a;
+    memset(&a, 0, sizeof a);
+    if (wn_layout(d, &a.L)) return -1;
+    if (!d_weights || !d_biases || !d_packed) return fail("weights/biases/packed must be non-NULL");
+    if ((uintptr_t)d_packed % 16) return fail("packed buffer must be 16-byte aligned");
+    for (int l = 0; l < a.L.n_layers; ++l) {
+        if (!d_weights[l] || !d_biases[l]) return fail("a weight or bias pointer is NULL");
+        a.w[l] = d_weights[l];
+        a.b[l] = d_biases[l];
+    }
+    a.packed = static_cast<uint32_t*>(d_packed);
+    if (hipError_t e0 = hipMemsetAsync(a.packed + a.L.status, 0, 16, stream); e0 != hipSuccess)
+        return hip_fail((int)e0, "drl_widenet_pack status reset");
+    const int e = drl::wn::launch_widenet_pack(a, stream);
+    return e == 0 ? 0 : hip_fail(e, "drl_widenet_pack launch");
+}
+
+int drl_widenet_act(const drl_widenet_desc* d, const void* d_packed, const void* d_input, int64_t num_envs,
+                    int64_t obs_stride, float epsilon, const float* d_epsilon, uint64_t seed, uint64_t step,
+                    int64_t env_offset, int32_t* d_actions, int64_t action_stride, float* d_q, int32_t* d_err,
+                    hipStream_t stream) {
+    drl::wn::ActArgs a;
+    memset(&a, 0, sizeof a);
+    if (wn_layout(d, &a.L)) return -1;
+    if (num_envs < 0) return fail("num_envs < 0");
+    if (num_envs == 0) return 0;
+    if (!d_packed || !d_input || !d_actions) return fail("packed/input/actions must be non-NULL");
+    if ((uintptr_t)d_packed % 16) return fail("packed buffer must be 16-byte aligned");
+    if (a.L.input == DRL_QNET_INPUT_CODE) {
+        if ((uintptr_t)d_input % 16) return fail("the policy code must be 16-byte aligned");
+    } else {
+        if ((uintptr_t)d_input % 8 || obs_stride % 2) return fail("obs rows must be 8-byte aligned (even obs_stride)");
+        if (obs_stride < d->in_features) return fail("obs_stride < in_features");
+    }
+    if ((uintptr_t)d_epsilon % 4) return fail("d_epsilon must be 4-byte aligned");
+    if ((uintptr_t)d_actions % 4 || (uintptr_t)d_q % 4 || (uintptr_t)d_err % 4)
+        return fail("actions, q and err must be 4-byte aligned");
+    if (action_stride < 1) return fail("action_stride must be >= 1");
+    a.packed = static_cast<const uint32_t*>(d_packed);
+    a.input = d_input;
+    a.obs_stride = obs_stride;
+    a.E = num_envs;
+    a.epsilon = epsilon;
+    a.eps_ptr = d_epsilon;
+    a.seed = seed;
+    a.step = step;
+    a.env_offset = env_offset;
+    a.actions = d_actions;
+    a.action_stride = action_stride;
+    a.q = d_q;
+    a.err = d_err;
+    a.n_actions = a.L.n_actions;
+    const int e = drl::wn::launch_widenet_act(a, num_cus(), stream);
+    return e == 0 ? 0 : hip_fail(e, "drl_widenet_act launch");
+}
+
+int drl_widenet_dqn_layout_query(const drl_widenet_desc* d, int32_t batch, drl_dqn_layout* layout) {
+    drl::wn::Layout L;
+    drl::ll::Plan P;
+    if (wn_plan(d, batch, &L, &P)) return -1;
+    if (!layout) return fail("layout is NULL");
+    *layout = P.pub;
+    return 0;
+}
+
+int drl_widenet_dqn_init(const drl_widenet_desc* d, int32_t batch, void* d_agent, float epsilon_start,
+                         hipStream_t stream) {
+    drl::wn::Layout L;
+    drl::ll::Plan P;
+    if (wn_plan(d, batch, &L, &P)) return -1;
+    if (!d_agent || (uintptr_t)d_agent % 16) return fail("the agent block must be a 16-byte aligned device pointer");
+    uint8_t* base = static_cast<uint8_t*>(d_agent);
+    // the moments; the init kernel sets the counters.  The scratch needs no clearing (drl_dqn_large_init).
+    if (hipError_t e = hipMemsetAsync(base + P.pub.m_off, 0, (size_t)(P.pub.counters_off - P.pub.m_off), stream);
+        e != hipSuccess)
+        return hip_fail((int)e, "drl_widenet_dqn_init moments");
+    hipError_t e = drl::launch_dqn_init(base + P.pub.counters_off, epsilon_start, stream);
+    return e == hipSuccess ? 0 : hip_fail((int)e, "drl_widenet_dqn_init launch");
+}
+
+int drl_widenet_dqn_train(const drl_widenet_desc* d, const drl_dqn_hparams* h, void* d_agent, void* d_packed,
+                          const drl_replay* r, int64_t size, hipStream_t stream) {
+    drl::wn::PackArgs pk;
+    memset(&pk, 0, sizeof pk);
+    drl::ll::LearnArgs a;
+    memset(&a, 0, sizeof a);
+    if (!h) {
+        if (wn_plan(d, 1, &pk.L, &a.P)) return -1;
+        return fail("hparams is NULL");
+    }
+    if (wn_plan(d, h->batch, &pk.L, &a.P)) return -1;
+    const drl::ll::Plan& P = a.P;
+    if (h->target_update_interval < 1 || h->epsilon_decay_every < 1)
+        return fail("target_update_interval and epsilon_decay_every must be >= 1");
+    if (!(h->beta1 >= 0.0 && h->beta1 < 1.0 && h->beta2 >= 0.0 && h->beta2 < 1.0))
+        return fail("beta1 and beta2 must be in [0, 1)");
+    if (!d_agent || (uintptr_t)d_agent % 16) return fail("the agent block must be a 16-byte aligned device pointer");
+    if (!d_packed || (uintptr_t)d_packed % 16) return fail("packed buffer must be a 16-byte aligned device pointer");
+    if (!r || !r->obs || !r->next_obs || !r->actions || !r->rewards || !r->dones) return fail("replay buffers are NULL");
+    if (r->capacity < 1 || r->capacity >= ((int64_t)1 << 31)) return fail("replay capacity must be in [1, 2^31)");
+    if (size < 0 || size > r->capacity) return fail("size must be in [0, capacity]");
+    if (P.code_w) {
+        if ((int64_t)r->obs_floats * 4 != drl::lay::code_bytes(P.code_w))
+            return fail("a DRL_QNET_INPUT_CODE net's replay rows are policy codes (drl_policy_code_bytes / 4 words)");
+    } else if (r->obs_floats < d->in_features) {
+        return fail("replay obs_floats < in_features");
+    }
+    if ((uintptr_t)r->obs % 4 || (uintptr_t)r->next_obs % 4) return fail("replay rows must be 4-byte aligned");
+    uint8_t* base = static_cast<uint8_t*>(d_agent);
+    a.trained = size >= h->batch;  // buffers.py:92-93 can_sample
+    a.code_w = P.code_w;
+    a.online = reinterpret_cast<float*>(base + P.pub.online_off);
+    a.target = reinterpret_cast<float*>(base + P.pub.target_off);
+    a.adam_m = reinterpret_cast<float*>(base + P.pub.m_off);
+    a.adam_v = reinterpret_cast<float*>(base + P.pub.v_off);
+    a.ctr = reinterpret_cast<drl::DqnCounters*>(base + P.pub.counters_off);
+    a.scratch = reinterpret_cast<float*>(base + P.pub.scratch_off);
+    a.r_obs = reinterpret_cast<const uint32_t*>(r->obs);
+    a.r_next = reinterpret_cast<const uint32_t*>(r->next_obs);
+    a.row_words = r->obs_floats;
+    a.r_act = r->actions;
+    a.r_rew = r->rewards;
+    a.r_done = r->dones;
+    a.size = size;
+    a.seed = h->sample_seed;
+    // the python floats as jax's weak typing rounds them into f32 arithmetic
+    a.gamma = (float)h->gamma;
+    a.b1 = (float)h->beta1;
+    a.b2 = (float)h->beta2;
+    a.c1 = (float)(1.0 - h->beta1);
+    a.c2 = (float)(1.0 - h->beta2);
+    a.adam_eps = (float)h->adam_eps;
+    a.neg_lr = (float)(-h->learning_rate);
+    a.tau = (float)h->tau;
+    a.one_minus_tau = (float)(1.0 - h->tau);
+    a.eps_decay = (float)h->epsilon_decay;
+    a.eps_end = (float)h->epsilon_end;
+    a.b1d = h->beta1;
+    a.b2d = h->beta2;
+    a.target_every = h->target_update_interval;
+    a.eps_every = h->epsilon_decay_every;
+    // the act's image of the new online set: the wide pack kernel on the online set, so the image is a fresh
+    // drl_widenet_pack's byte for byte; the counters kernel clears the status vector (kernel nodes only)
+    for (int l = 0; l < P.n_layers; ++l) {
+        pk.w[l] = a.online + P.woff[l];
+        pk.b[l] = a.online + P.boff[l];
+    }
+    pk.packed = static_cast<uint32_t*>(d_packed);
+    a.pack_status = pk.packed + pk.L.status;
+    if (const int e = drl::ll::launch_large_train(a, stream); e != 0)
+        return hip_fail(e, "drl_widenet_dqn_train launch");
+    const int e = drl::wn::launch_widenet_pack(pk, stream);
+    return e == 0 ? 0 : hip_fail(e, "drl_widenet_dqn_train pack launch");
+}
+
+int drl_widenet_dqn_sample_rows(const drl_widenet_desc* d, const drl_dqn_hparams* h, const void* d_agent,
+                                int64_t size, int64_t* d_slots, hipStream_t stream) {
+    drl::wn::Layout L;
+    drl::ll::Plan P;
+    if (!h) {
+        if (wn_plan(d, 1, &L, &P)) return -1;
+        return fail("hparams is NULL");
+    }
+    if (wn_plan(d, h->batch, &L, &P)) return -1;
+    if (!d_agent || (uintptr_t)d_agent % 16) return fail("the agent block must be a 16-byte aligned device pointer");
+    if (!d_slots || (uintptr_t)d_slots % 8) return fail("d_slots must be an 8-byte aligned device pointer");
+    if (size < 1) return fail("size must be >= 1 (buffers.py can_sample: nothing is drawn from an empty ring)");
+    const int e = drl::ll::launch_large_sample(static_cast<const uint8_t*>(d_agent) + P.pub.counters_off, h->sample_seed,
+                                               h->batch, size, d_slots, stream);
+    return e == 0 ? 0 : hip_fail(e, "drl_widenet_dqn_sample_rows launch");
+}
+
+}  // extern "C"

@@ -543,6 +543,186 @@ class ConvQNetwork:
             raise DroneRLError(f"convnet error bits {e:#x}")
 
 
+class DrlWidenetDesc(ctypes.Structure):
+    _fields_ = [("in_features", ctypes.c_int32), ("n_hidden", ctypes.c_int32), ("hidden", ctypes.c_int32 * 3),
+                ("n_actions", ctypes.c_int32), ("input", ctypes.c_int32)]
+
+
+WIDENET_MAX_WIDTH = 256  # DRL_WIDENET_MAX_WIDTH
+QNET_MAX_WIDTH = 128     # drl_qnet_desc's hidden widths
+
+
+def _bind_widenet(L):
+    if getattr(L, "_widenet_ready", False):
+        return L
+    i32, i64, u64, f32 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float
+    D, PP = ctypes.POINTER(DrlWidenetDesc), ctypes.POINTER(_vp)
+    sig = {
+        "drl_widenet_packed_bytes": [D, ctypes.POINTER(i64)],
+        "drl_widenet_pack": [D, PP, PP, _vp, _vp],
+        "drl_widenet_act": [D, _vp, _vp, i64, i64, f32, _vp, u64, u64, i64, _vp, i64, _vp, _vp, _vp],
+        "drl_widenet_dqn_layout_query": [D, i32, ctypes.POINTER(DrlDqnLayout)],
+        "drl_widenet_dqn_init": [D, i32, _vp, f32, _vp],
+        "drl_widenet_dqn_train": [D, ctypes.POINTER(DrlDqnHParams), _vp, _vp, ctypes.POINTER(DrlReplay), i64, _vp],
+        "drl_widenet_dqn_sample_rows": [D, ctypes.POINTER(DrlDqnHParams), _vp, i64, _vp, _vp],
+    }
+    for name, args in sig.items():
+        f = getattr(L, name)
+        f.argtypes = args
+        f.restype = ctypes.c_int
+    L._widenet_ready = True
+    return L
+
+
+def is_wide(hidden: Sequence[int]) -> bool:
+    """Hidden widths that need the wide path: any above QNetwork's 128."""
+    return any(int(w) > QNET_MAX_WIDTH for w in hidden)
+
+
+class WideQNetwork:
+    """Dense Q-network with hidden widths up to 256 (run_jax_sweep.py's
+    (256, 128, 64) agent): QNetwork's net, constructor arguments, attributes
+    and initialisation (1 to 3 widths, each a multiple of 8 in [8, 256]), f32
+    numerics only (QNetwork's "f32": split fp16 hi/lo operands, three MFMAs per
+    product tile).  The packed image (up to ~1.1 MB) does not fit a CU's LDS,
+    so `act` (drl_widenet_act) reads the weight fragments from L2; narrow nets
+    are accepted but run faster as a QNetwork, where checkpoint.to_qnet and
+    train keep them.  `act` has ConvQNetwork.act's signature and QNetwork.act's
+    exploration stream; input "code" (a 5x5, 7x7 or 9x9 window) reads drone
+    0's policy code, with Q bit for bit the "obs" net's.  WideDQNLearner
+    trains the net on the device."""
+
+    precision = "f32"
+
+    def __init__(self, in_features: int, hidden: Sequence[int] = (256, 128, 64), n_actions: int = NUM_ACTIONS,
+                 device=None, generator: Optional[torch.Generator] = None, input: str = "obs"):
+        if input not in INPUTS:
+            raise ValueError(f"input must be one of {sorted(INPUTS)}")
+        self.in_features, self.hidden, self.n_actions = int(in_features), tuple(int(w) for w in hidden), int(n_actions)
+        if not 1 <= len(self.hidden) <= 3:
+            raise ValueError("hidden: 1 to 3 widths (n_hidden)")
+        self.desc = DrlWidenetDesc(self.in_features, len(self.hidden),
+                                   (ctypes.c_int32 * 3)(*self.hidden, *[0] * (3 - len(self.hidden))),
+                                   self.n_actions, INPUTS[input])
+        self.L = _bind_widenet(_bind(lib()))
+        nb = ctypes.c_int64()
+        if self.L.drl_widenet_packed_bytes(ctypes.byref(self.desc), ctypes.byref(nb)):
+            raise ValueError(self.L.drl_last_error().decode())
+        self.input = input
+        self.code_bytes = 0
+        if input == "code":
+            w = round((self.in_features / 6) ** 0.5)
+            self.code_bytes = int(lib().drl_policy_code_bytes((w - 1) // 2))
+        self.device = torch.device(device if device is not None else "cuda")
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        sizes = [self.in_features, *self.hidden, self.n_actions]
+        self.weights, self.biases = [], []
+        for i in range(len(sizes) - 1):
+            # he_normal for the hidden layers (dqn.py:53), flax Dense's lecun_normal for the output
+            w = flax_kernel_init((sizes[i + 1], sizes[i]), 2.0 if i < len(sizes) - 2 else 1.0, generator)
+            self.weights.append(w.to(self.device))
+            self.biases.append(torch.zeros(sizes[i + 1], device=self.device))
+        self.packed = torch.empty(nb.value // 4, dtype=torch.int32, device=self.device)  # 16-B aligned
+        self.err = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.pack()
+
+    def load(self, weights: Sequence[torch.Tensor], biases: Sequence[torch.Tensor]):
+        """Set parameters (torch layout [out][in]) and re-pack.  Nothing
+        changes if they are refused."""
+        if len(weights) != len(self.weights) or len(biases) != len(self.biases):
+            raise ValueError("layer count mismatch")
+        for i, (w, b) in enumerate(zip(weights, biases)):
+            if tuple(w.shape) != tuple(self.weights[i].shape) or tuple(b.shape) != tuple(self.biases[i].shape):
+                raise ValueError(f"layer {i}: shape {tuple(w.shape)} != {tuple(self.weights[i].shape)}")
+        ws = [w.detach().to(self.device, torch.float32) for w in weights]
+        bs = [b.detach().to(self.device, torch.float32) for b in biases]
+        self._validate(ws, bs)
+        for i, (w, b) in enumerate(zip(ws, bs)):
+            # (in place: a WideDQNLearner's net holds views of its agent block)
+            self.weights[i].copy_(w)
+            self.biases[i].copy_(b)
+        self.pack()
+
+    def _validate(self, weights, biases):
+        for t in (*weights, *biases):
+            if not bool(torch.isfinite(t).all()):
+                raise ValueError("weights and biases must be finite")
+        for t in weights:  # the weights are split into fp16 pieces; the biases stay f32
+            if float(t.abs().max()) >= 65504.0:
+                raise ValueError("the f32 act needs |w| < 65504")
+
+    def pack(self):
+        self._validate(self.weights, self.biases)
+        n = len(self.weights)
+        wp = (_vp * n)(*[w.data_ptr() for w in self.weights])
+        bp = (_vp * n)(*[b.data_ptr() for b in self.biases])
+        _check(self.L, self.L.drl_widenet_pack(ctypes.byref(self.desc), wp, bp, _vp(self.packed.data_ptr()),
+                                               _stream(self.device)))
+
+    def reference_q(self, obs: torch.Tensor) -> torch.Tensor:
+        """Plain torch f32 forward (checker for tests)."""
+        x = obs.reshape(obs.shape[0], -1)[:, :self.in_features].to(torch.float32)
+        for i, (w, b) in enumerate(zip(self.weights, self.biases)):
+            x = x @ w.to(x.device).t() + b.to(x.device)
+            if i < len(self.weights) - 1:
+                x = torch.relu(x)
+        return x
+
+    def act(self, obs: torch.Tensor, epsilon, seed: int = 0, step: int = 0, env_offset: int = 0,
+            actions: Optional[torch.Tensor] = None, q_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Epsilon-greedy action for each row of obs [E, ..., in_features]
+        (input "code": the policy code, uint8 [E, code_bytes]); the arguments
+        and the return value are ConvQNetwork.act's.  epsilon: a float, or a
+        float32 device tensor of one element read by the kernel."""
+        E = obs.shape[0]
+        if self.input == "code":
+            _on(obs, self.device, torch.uint8, "code")
+            if tuple(obs.shape) != (E, self.code_bytes) or not obs.is_contiguous():
+                raise ValueError(f"code must be a contiguous uint8 [E, {self.code_bytes}] tensor")
+            x, stride = obs, 0
+        else:
+            _on(obs, self.device, torch.float32, "obs")
+            x = obs.reshape(E, -1)
+            if x.shape[1] < self.in_features or x.stride(1) != 1:
+                raise ValueError("obs must hold at least in_features contiguous float32 values per env")
+            stride = x.stride(0)
+        if actions is None:
+            actions = torch.empty((E, 1), dtype=torch.int32, device=self.device)
+        _on(actions, self.device, torch.int32, "actions")
+        if actions.shape[0] != E or actions.dim() > 2 or not actions.is_contiguous():
+            raise ValueError("actions must be a contiguous int32 [E] or [E, n] tensor")
+        if q_out is not None:
+            _on(q_out, self.device, torch.float32, "q_out")
+            if tuple(q_out.shape) != (E, self.n_actions) or not q_out.is_contiguous():
+                raise ValueError(f"q_out must be a contiguous float32 [{E}, {self.n_actions}] tensor")
+        stride_a = actions.shape[1] if actions.dim() == 2 else 1
+        eps_ptr = None
+        if isinstance(epsilon, torch.Tensor):
+            _on(epsilon, self.device, torch.float32, "epsilon")
+            if epsilon.numel() != 1:
+                raise ValueError("a device epsilon must be one float32 element")
+            eps_ptr, epsilon = _vp(epsilon.data_ptr()), 0.0
+        _check(self.L, self.L.drl_widenet_act(
+            ctypes.byref(self.desc), _vp(self.packed.data_ptr()), _vp(x.data_ptr()), E, stride, float(epsilon),
+            eps_ptr, seed & (2**64 - 1), step, env_offset, _vp(actions.data_ptr()), stride_a,
+            None if q_out is None else _vp(q_out.data_ptr()), _vp(self.err.data_ptr()), _stream(self.device)))
+        return actions
+
+    def check_errors(self):
+        """Synchronise and raise if an act met an input or a hidden
+        activation outside fp16's split range (|v| >= 65520, or NaN), or a
+        packed weight outside it: its Q values and greedy actions are then not
+        valid (DRL_ERR_QNET_RANGE)."""
+        e = int(self.err.item())
+        if e:
+            self.err.zero_()
+            if e & DRL_ERR_QNET_RANGE:
+                raise DroneRLError("wide act: an input or hidden activation is outside the fp16 split range "
+                                   "(|v| >= 65520 or NaN); Q values are not valid")
+            raise DroneRLError(f"widenet error bits {e:#x}")
+
+
 def decode_policy_code(code: torch.Tensor, window_radius: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Policy-code rows uint8 [n, code_bytes] -> drone 0's observation f32
     [n, W*W*6], bit for bit what drl_obs writes (drl_code_decode)."""
@@ -878,12 +1058,18 @@ class LargeBatchDQNLearner(DQNLearner):
     synchronisation and no wait between workgroups, so `train` is
     graph-capturable.  The surface is DQNLearner's without `train(fresh=)`."""
 
+    _abi = "drl_dqn_large"  # the C calls: <_abi>_layout_query, _init, _train, _sample_rows
+    _bound = staticmethod(_bind)
+
+    def _call(self, name):
+        return getattr(self.L, f"{self._abi}_{name}")
+
     def __init__(self, net: QNetwork, hp: Optional[DQNHParams] = None, target=None,
                  generator: Optional[torch.Generator] = None):
         self.net, self.hp = net, hp or DQNHParams()
-        self.L = _bind(net.L)
+        self.L = self._bound(net.L)
         lay = DrlDqnLayout()
-        if self.L.drl_dqn_large_layout_query(ctypes.byref(net.desc), self.hp.batch, ctypes.byref(lay)):
+        if self._call("layout_query")(ctypes.byref(net.desc), self.hp.batch, ctypes.byref(lay)):
             raise ValueError(self.L.drl_last_error().decode())
         self.layout = lay
         dev = net.device
@@ -918,9 +1104,9 @@ class LargeBatchDQNLearner(DQNLearner):
         rows for a "code" one."""
         if rb.obs.device != self.block.device:
             raise ValueError("the replay buffer must be on the learner's device")
-        _check(self.L, self.L.drl_dqn_large_train(ctypes.byref(self.net.desc), ctypes.byref(self._hp),
-                                                  _vp(self.block.data_ptr()), _vp(self.net.packed.data_ptr()),
-                                                  ctypes.byref(rb._c), rb.size, _stream(self.block.device)))
+        _check(self.L, self._call("train")(ctypes.byref(self.net.desc), ctypes.byref(self._hp),
+                                           _vp(self.block.data_ptr()), _vp(self.net.packed.data_ptr()),
+                                           ctypes.byref(rb._c), rb.size, _stream(self.block.device)))
 
     def sample_slots(self, size: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The replay slots (int64 [batch], in [0, size)) the next train()
@@ -930,9 +1116,9 @@ class LargeBatchDQNLearner(DQNLearner):
         _on(out, self.block.device, torch.int64, "out")
         if out.numel() != self.hp.batch or not out.is_contiguous():
             raise ValueError(f"out must be a contiguous int64 [{self.hp.batch}] tensor")
-        _check(self.L, self.L.drl_dqn_large_sample_rows(ctypes.byref(self.net.desc), ctypes.byref(self._hp),
-                                                        _vp(self.block.data_ptr()), int(size), _vp(out.data_ptr()),
-                                                        _stream(self.block.device)))
+        _check(self.L, self._call("sample_rows")(ctypes.byref(self.net.desc), ctypes.byref(self._hp),
+                                                 _vp(self.block.data_ptr()), int(size), _vp(out.data_ptr()),
+                                                 _stream(self.block.device)))
         return out
 
     def check_errors(self):
@@ -940,7 +1126,7 @@ class LargeBatchDQNLearner(DQNLearner):
         outside the fp16 split range (the learner's launches wait for nothing,
         so there is no timeout to report)."""
         if self.net.precision == "f32" and int(self.net.packed[-4].item()):
-            raise DroneRLError("drl_dqn_large_train: a learned weight left the f32 act's range (|w| >= 65504 or "
+            raise DroneRLError(f"{self._abi}_train: a learned weight left the f32 act's range (|w| >= 65504 or "
                                "not finite); the act's Q values are not valid")
 
     def restart(self, epsilon: Optional[float] = None):
@@ -948,14 +1134,29 @@ class LargeBatchDQNLearner(DQNLearner):
         the counters from zero (step 0, epsilon `epsilon` or
         hp.epsilon_start).  The online and target parameters are kept."""
         eps = self.hp.epsilon_start if epsilon is None else float(epsilon)
-        _check(self.L, self.L.drl_dqn_large_init(ctypes.byref(self.net.desc), self.hp.batch,
-                                                 _vp(self.block.data_ptr()), eps, _stream(self.block.device)))
+        _check(self.L, self._call("init")(ctypes.byref(self.net.desc), self.hp.batch,
+                                          _vp(self.block.data_ptr()), eps, _stream(self.block.device)))
 
 
-def make_learner(net: QNetwork, hp: Optional[DQNHParams] = None, **kw):
-    """The dense nets' learner for hp.batch: DQNLearner (one launch, batches up
-    to 64) or LargeBatchDQNLearner (a launch chain, batches up to 4096)."""
+class WideDQNLearner(LargeBatchDQNLearner):
+    """LargeBatchDQNLearner for a WideQNetwork (hidden widths up to 256):
+    the same launch chain, agent block, semantics and arithmetic
+    (drl_widenet_dqn_train; bit for bit LargeBatchDQNLearner's at the widths
+    both take), batches 1 to 4096, graph-capturable; the act's image is
+    refreshed by the wide pack kernel in the same call."""
+
+    _abi = "drl_widenet_dqn"
+    _bound = staticmethod(lambda L: _bind_widenet(_bind(L)))
+
+
+def make_learner(net, hp: Optional[DQNHParams] = None, **kw):
+    """The dense nets' learner: for a QNetwork by hp.batch, DQNLearner (one
+    launch, batches up to 64) or LargeBatchDQNLearner (a launch chain, batches
+    up to 4096); for a WideQNetwork, WideDQNLearner (the launch chain at every
+    batch)."""
     hp = hp or DQNHParams()
+    if isinstance(net, WideQNetwork):
+        return WideDQNLearner(net, hp, **kw)
     cls = DQNLearner if hp.batch <= DQN_MAX_BATCH else LargeBatchDQNLearner
     return cls(net, hp, **kw)
 

@@ -7,7 +7,8 @@ device epsilon), the env step writing drone 0's next policy code and landing
 the drone-0 transitions in the replay ring (drl_step_code_replay:
 buffer.add_many), the learner block (drl_dqn_train: sample + train_step when
 the buffer can sample, the target update, the epsilon decay, step + 1; a
-conv net: drl_convnet_act and drl_convnet_dqn_train), and
+conv net: drl_convnet_act and drl_convnet_dqn_train; a dense net wider than
+128: drl_widenet_act and drl_widenet_dqn_train), and
 a reset of every env when step % reset_env_every == 0 (:99-113).
 `evaluate` is eval_jax (:270-319): greedy drone 0 against random drones,
 episodes sharded over ranks with the eval table all-reduced
@@ -45,10 +46,13 @@ def train(params: EnvParams, num_envs: int, num_steps: int, hidden: Sequence[int
     """train_jax.py's training loop (see the module docstring).  hp: a
     dqn.DQNHParams (default: train_jax.py's defaults with num_steps, so
     epsilon decays as :133-134 schedules it).  hidden: 1-3 widths, each a
-    multiple of 8 in [8, 128] (train_jax.py's default net is (16, 16)).
-    hp.batch (--batch_size): 1..4096 for dense nets (dqn.make_learner: the
-    single-launch learner up to 64, the large-batch one above), 1..64 for
-    conv nets.
+    multiple of 8 in [8, 256] (train_jax.py's default net is (16, 16),
+    run_jax_sweep.py's (256, 128, 64)); with a width above 128 the net is a
+    dqn.WideQNetwork trained by dqn.WideDQNLearner (one GPU only), otherwise
+    today's QNetwork path.  hp.batch (--batch_size): 1..4096 for dense nets
+    (dqn.make_learner: the single-launch learner up to 64, the large-batch
+    one above; a wide net: the launch chain at every batch), 1..64 for conv
+    nets.
 
     network_type "conv" (train_jax.py --network_type conv): a ConvQNetwork
     of conv_layers (the reference's tuple of dicts; default train_jax.py's
@@ -62,7 +66,8 @@ def train(params: EnvParams, num_envs: int, num_steps: int, hidden: Sequence[int
     replay ring is sharded (global_learner.ShardedReplay) and every rank runs
     the same learner; env_offset is then ignored.  The returned rate counts
     every rank's envs."""
-    from .dqn import ConvDQNLearner, ConvQNetwork, DQNHParams, QNetwork, ReplayBuffer, make_learner
+    from .dqn import (ConvDQNLearner, ConvQNetwork, DQNHParams, QNetwork, ReplayBuffer, WideQNetwork, is_wide,
+                      make_learner)
     from .distributed import shard_envs
     from .env import BatchedDeliveryDrones
     from .global_learner import ShardedReplay
@@ -72,6 +77,9 @@ def train(params: EnvParams, num_envs: int, num_steps: int, hidden: Sequence[int
         raise ValueError("network_type must be 'dense' or 'conv'")
     if network_type == "conv" and world > 1:
         raise ValueError(CONV_SHARDING_REFUSAL)
+    wide = network_type == "dense" and is_wide(hidden)
+    if wide and world > 1:
+        raise ValueError(WIDE_SHARDING_REFUSAL)
     shard = shard_envs(num_envs, rank, world) if world > 1 else None
     env = BatchedDeliveryDrones(params, shard.num_envs if shard else num_envs, device=device,
                                 env_offset=shard.env_offset if shard else env_offset)
@@ -87,6 +95,9 @@ def train(params: EnvParams, num_envs: int, num_steps: int, hidden: Sequence[int
                            tuple(conv_dense_layers), device=dev, generator=torch.Generator().manual_seed(seed),
                            input="code")
         learner = ConvDQNLearner(net, hp, generator=torch.Generator().manual_seed(seed + 1))
+    elif wide:  # (a width above 128: the wide act and the launch-chain learner, dqn.WideDQNLearner)
+        net = WideQNetwork(D, tuple(hidden), device=dev, generator=torch.Generator().manual_seed(seed), input="code")
+        learner = make_learner(net, hp, generator=torch.Generator().manual_seed(seed + 1))
     else:
         net = QNetwork(D, tuple(hidden), device=dev, generator=torch.Generator().manual_seed(seed), input="code")
         # (batches up to 64: DQNLearner's one launch; up to 4096: LargeBatchDQNLearner's launch chain)
@@ -108,7 +119,7 @@ def train(params: EnvParams, num_envs: int, num_steps: int, hidden: Sequence[int
         b, nb = t & 1, (t + 1) & 1
         # drones 1..N-1 act at random (train_jax.py:42-49): written by the act beside drone 0's action when the
         # step reads them, or drawn by the step itself (drl_step_code_replay_synth; the same counter hash)
-        if network_type == "conv":
+        if network_type == "conv" or wide:
             net.act(code[b], learner.epsilon, seed=act_seed, step=t, env_offset=env.env_offset, actions=acts)
         else:
             net.act(code[b], learner.epsilon, seed=act_seed, step=t, env_offset=env.env_offset, actions=acts,
@@ -138,6 +149,8 @@ def train(params: EnvParams, num_envs: int, num_steps: int, hidden: Sequence[int
 
 CONV_SHARDING_REFUSAL = ("--use_sharding with --network_type conv is not implemented: the global (sharded) "
                          "learner trains dense nets only")
+WIDE_SHARDING_REFUSAL = ("--use_sharding with --hidden_layers wider than 128 is not implemented: the global "
+                         "(sharded) learner trains dense nets of widths up to 128 only")
 
 
 def greedy_policy(qnet):
@@ -166,11 +179,12 @@ def parse_args(argv=None):
     """train_jax.py's command line (:335-390) for the options this driver
     implements: the env, training and eval options and
     --save_final_checkpoint; the dense net's widths are multiples of 8 in
-    [8, 128] (1-3 layers), so train_jax.py's default `--hidden_layers 16 16`
-    runs as it is.  --hidden_layers here defaults to the benchmark net
-    (128, 64): a choice (what this command has always trained), no longer a
-    limit of the device act.  --use_sharding runs under torchrun (one process
-    per GPU)."""
+    [8, 256] (1-3 layers), so train_jax.py's default `--hidden_layers 16 16`
+    and run_jax_sweep.py's `256 128 64` run as they are (a width above 128:
+    the wide path, dqn.WideQNetwork; not with --use_sharding).
+    --hidden_layers here defaults to the benchmark net (128, 64): a choice
+    (what this command has always trained), no longer a limit of the device
+    act.  --use_sharding runs under torchrun (one process per GPU)."""
     import argparse
     ap = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     ap.add_argument("--n_drones", type=int, default=4)
@@ -224,6 +238,8 @@ def parse_args(argv=None):
         raise ValueError("When using --use_sharding you need to provide num_envs > 1")
     if args.use_sharding and args.network_type == "conv":
         raise ValueError(CONV_SHARDING_REFUSAL)
+    if args.use_sharding and args.network_type == "dense" and max(args.hidden_layers) > 128:
+        raise ValueError(WIDE_SHARDING_REFUSAL)
     return args
 
 
@@ -300,10 +316,13 @@ def main(argv=None) -> dict:
                 res.learner.save(path, format=fmt)
             metrics[f"checkpoint_{fmt}"] = path
     # the final eval with the trained net (the online parameters, as eval_jax uses ag_state)
-    from .dqn import ConvQNetwork, QNetwork
+    from .dqn import ConvQNetwork, QNetwork, WideQNetwork
     if args.network_type == "conv":
         qnet = ConvQNetwork(res.net.obs_shape, res.net.conv_layers, res.net.dense_layers, device=dev)
         qnet.load(res.net.conv_weights, res.net.conv_biases, res.net.weights, res.net.biases)
+    elif isinstance(res.net, WideQNetwork):
+        qnet = WideQNetwork(res.net.in_features, res.net.hidden, device=dev)
+        qnet.load(*zip(*res.learner.params("online")))
     else:
         qnet = QNetwork(res.net.in_features, res.net.hidden, device=dev, precision="f32")
         qnet.load(*zip(*res.learner.params("online")))

@@ -748,6 +748,71 @@ int drl_convnet_dqn_train(const drl_convnet_desc* d, const drl_dqn_hparams* h, v
 int drl_convnet_dqn_sample_rows(const drl_convnet_desc* d, const drl_dqn_hparams* h, const void* d_agent,
                                 int64_t size, int64_t* d_slots, hipStream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Wide dense Q-networks: hidden widths up to DRL_WIDENET_MAX_WIDTH
+ * (run_jax_sweep.py trains hidden_layers = (256, 128, 64)), beside drl_qnet_*
+ * whose act kernels keep layer 0 in LDS and stop at 128.  The same net
+ * (in_features -> hidden... (ReLU) -> n_actions, torch layout [out][in]) with
+ * DRL_QNET_F32's numerics: every operand v split into fp16 hi = fp16(v) and
+ * lo = fp16((v - hi) * 2^11), three MFMAs per product tile, the layer's value
+ * (acc + 2^-11 acl) + bias; Q matches an f32 forward to f32 rounding.  The
+ * packed image (up to ~1.1 MB) does not fit a CU's LDS: the act reads its
+ * weight fragments from global memory (L2), each read serving every env tile
+ * of the workgroup.  The description takes narrow nets too.
+ * Limits (each refused by name, by every call below): in_features even in
+ * [2, 512]; 1..3 hidden widths, multiples of 8 in [8, DRL_WIDENET_MAX_WIDTH];
+ * n_actions in [1, 8]; input DRL_QNET_INPUT_OBS, or DRL_QNET_INPUT_CODE with
+ * in_features = W*W*6 for W in 5, 7, 9.
+ * ------------------------------------------------------------------------ */
+#define DRL_WIDENET_MAX_WIDTH 256
+typedef struct drl_widenet_desc {
+    int32_t in_features;  /* even, 2..512 */
+    int32_t n_hidden;     /* 1..3 */
+    int32_t hidden[3];    /* multiples of 8 in [8, DRL_WIDENET_MAX_WIDTH] */
+    int32_t n_actions;    /* 1..8 */
+    int32_t input;        /* DRL_QNET_INPUT_OBS or DRL_QNET_INPUT_CODE (5x5, 7x7, 9x9 window) */
+} drl_widenet_desc;
+
+/* Bytes of the packed network (opaque: every layer's fp16 hi and lo MFMA
+ * fragments with widths and K padded with zeros, f32 biases, a 16-byte status
+ * vector). */
+int drl_widenet_packed_bytes(const drl_widenet_desc* d, int64_t* bytes);
+/* drl_qnet_pack's arguments: d_weights[l] [out][in] and d_biases[l] [out], f32,
+ * host arrays of n_hidden + 1 device pointers.  A weight with |w| >= 65504 (or
+ * not finite) sets the image's status word, which every act then reports as
+ * DRL_ERR_QNET_RANGE.  d_packed: 16-byte aligned. */
+int drl_widenet_pack(const drl_widenet_desc* d, const float* const* d_weights, const float* const* d_biases,
+                     void* d_packed, hipStream_t stream);
+/* drl_convnet_act's arguments and rule: the epsilon-greedy choice on the net's
+ * Q values, one launch for every env, with the other acts' exploration stream
+ * (the counter hash of (seed, step, env_offset + e); the first maximum on
+ * ties).  d_input: f32 rows of obs_stride floats (8-byte aligned, obs_stride
+ * even and >= in_features) for a DRL_QNET_INPUT_OBS net; drone index 0's
+ * policy code (drl_policy_code_bytes per env, 16-byte aligned; obs_stride
+ * ignored) for a DRL_QNET_INPUT_CODE net, decoded exactly as drl_code_decode
+ * does, so Q is bit for bit the obs net's.  d_epsilon (nullable): the
+ * exploration rate read on the device instead of `epsilon`.  d_q (nullable):
+ * f32 [num_envs][n_actions].  d_err (nullable): OR-ed DRL_ERR_QNET_RANGE when
+ * an input or a hidden activation has |v| >= 65520 or is NaN.  Allocates
+ * nothing, does not synchronise, no workgroup waits for another. */
+int drl_widenet_act(const drl_widenet_desc* d, const void* d_packed, const void* d_input, int64_t num_envs,
+                    int64_t obs_stride, float epsilon, const float* d_epsilon, uint64_t seed, uint64_t step,
+                    int64_t env_offset, int32_t* d_actions, int64_t action_stride, float* d_q, int32_t* d_err,
+                    hipStream_t stream);
+/* The learner: drl_dqn_large_*'s launch chain, agent block (drl_dqn_layout),
+ * semantics and arithmetic (bit for bit at the widths both take) for a
+ * drl_widenet_desc; batch in [1, DRL_DQN_LARGE_MAX_BATCH].  After
+ * drl_widenet_dqn_train d_packed is byte for byte drl_widenet_pack of the
+ * online set.  Nothing is allocated, nothing synchronises, no workgroup waits
+ * for another, no float atomic is used: the calls are graph-capturable. */
+int drl_widenet_dqn_layout_query(const drl_widenet_desc* d, int32_t batch, drl_dqn_layout* layout);
+int drl_widenet_dqn_init(const drl_widenet_desc* d, int32_t batch, void* d_agent, float epsilon_start,
+                         hipStream_t stream);
+int drl_widenet_dqn_train(const drl_widenet_desc* d, const drl_dqn_hparams* h, void* d_agent, void* d_packed,
+                          const struct drl_replay* r, int64_t size, hipStream_t stream);
+int drl_widenet_dqn_sample_rows(const drl_widenet_desc* d, const drl_dqn_hparams* h, const void* d_agent,
+                                int64_t size, int64_t* d_slots, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
