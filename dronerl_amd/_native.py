@@ -48,6 +48,9 @@ EXPORTS = ["drl_abi_version", "drl_last_error", "drl_side_from_density", "drl_la
            # the conv nets' DQN learner (dronerl_amd.dqn.ConvDQNLearner)
            "drl_convnet_dqn_layout_query", "drl_convnet_dqn_init", "drl_convnet_dqn_train",
            "drl_convnet_dqn_sample_rows",
+           # ... at batches up to 4096 (dronerl_amd.dqn.LargeBatchConvDQNLearner)
+           "drl_convnet_dqn_large_layout_query", "drl_convnet_dqn_large_init", "drl_convnet_dqn_large_train",
+           "drl_convnet_dqn_large_sample_rows",
            # the dense nets' learner at batches up to 4096 (dronerl_amd.dqn.LargeBatchDQNLearner)
            "drl_dqn_large_layout_query", "drl_dqn_large_init", "drl_dqn_large_train", "drl_dqn_large_sample_rows",
            # dense nets with hidden widths up to 256 (dronerl_amd.dqn.WideQNetwork, WideDQNLearner)

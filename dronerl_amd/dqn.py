@@ -330,6 +330,8 @@ def _bind_convnet(L):
         "drl_convnet_dqn_train": [D, ctypes.POINTER(DrlDqnHParams), _vp, _vp, ctypes.POINTER(DrlReplay), i64, _vp],
         "drl_convnet_dqn_sample_rows": [D, ctypes.POINTER(DrlDqnHParams), _vp, i64, _vp, _vp],
     }
+    for call in ("layout_query", "init", "train", "sample_rows"):  # the same argument lists at batches up to 4096
+        sig[f"drl_convnet_dqn_large_{call}"] = sig[f"drl_convnet_dqn_{call}"]
     for name, args in sig.items():
         f = getattr(L, name)
         f.argtypes = args
@@ -1150,13 +1152,17 @@ class WideDQNLearner(LargeBatchDQNLearner):
 
 
 def make_learner(net, hp: Optional[DQNHParams] = None, **kw):
-    """The dense nets' learner: for a QNetwork by hp.batch, DQNLearner (one
-    launch, batches up to 64) or LargeBatchDQNLearner (a launch chain, batches
-    up to 4096); for a WideQNetwork, WideDQNLearner (the launch chain at every
-    batch)."""
+    """A net's learner: for a QNetwork by hp.batch, DQNLearner (one launch,
+    batches up to 64) or LargeBatchDQNLearner (a launch chain, batches up to
+    4096); for a WideQNetwork, WideDQNLearner (the launch chain at every
+    batch); for a ConvQNetwork by hp.batch, ConvDQNLearner (batches up to 64)
+    or LargeBatchConvDQNLearner (chunked gradients, batches up to 4096)."""
     hp = hp or DQNHParams()
     if isinstance(net, WideQNetwork):
         return WideDQNLearner(net, hp, **kw)
+    if isinstance(net, ConvQNetwork):
+        cls = ConvDQNLearner if hp.batch <= CONV_DQN_MAX_BATCH else LargeBatchConvDQNLearner
+        return cls(net, hp, **kw)
     cls = DQNLearner if hp.batch <= DQN_MAX_BATCH else LargeBatchDQNLearner
     return cls(net, hp, **kw)
 
@@ -1176,12 +1182,17 @@ class ConvDQNLearner:
     reference's own key gives it (flax Conv / Dense default lecun_normal with
     fan_in k*k*cin, zero biases)."""
 
+    _abi = "drl_convnet_dqn"  # the C calls: <_abi>_layout_query, _init, _train, _sample_rows
+
+    def _call(self, name):
+        return getattr(self.L, f"{self._abi}_{name}")
+
     def __init__(self, net: ConvQNetwork, hp: Optional[DQNHParams] = None, target=None,
                  generator: Optional[torch.Generator] = None):
         self.net, self.hp = net, hp or DQNHParams()
         self.L = _bind(_bind_convnet(net.L))
         lay = DrlConvnetDqnLayout()
-        if self.L.drl_convnet_dqn_layout_query(ctypes.byref(net.desc), self.hp.batch, ctypes.byref(lay)):
+        if self._call("layout_query")(ctypes.byref(net.desc), self.hp.batch, ctypes.byref(lay)):
             raise ValueError(self.L.drl_last_error().decode())
         self.layout = lay
         dev = net.device
@@ -1238,9 +1249,9 @@ class ConvDQNLearner:
         rows for a "code" one."""
         if rb.obs.device != self.block.device:
             raise ValueError("the replay buffer must be on the learner's device")
-        _check(self.L, self.L.drl_convnet_dqn_train(ctypes.byref(self.net.desc), ctypes.byref(self._hp),
-                                                    _vp(self.block.data_ptr()), _vp(self.net.packed.data_ptr()),
-                                                    ctypes.byref(rb._c), rb.size, _stream(self.block.device)))
+        _check(self.L, self._call("train")(ctypes.byref(self.net.desc), ctypes.byref(self._hp),
+                                           _vp(self.block.data_ptr()), _vp(self.net.packed.data_ptr()),
+                                           ctypes.byref(rb._c), rb.size, _stream(self.block.device)))
 
     def sample_slots(self, size: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The replay slots (int64 [batch], in [0, size)) the next train()
@@ -1250,9 +1261,9 @@ class ConvDQNLearner:
         _on(out, self.block.device, torch.int64, "out")
         if out.numel() != self.hp.batch or not out.is_contiguous():
             raise ValueError(f"out must be a contiguous int64 [{self.hp.batch}] tensor")
-        _check(self.L, self.L.drl_convnet_dqn_sample_rows(ctypes.byref(self.net.desc), ctypes.byref(self._hp),
-                                                          _vp(self.block.data_ptr()), int(size), _vp(out.data_ptr()),
-                                                          _stream(self.block.device)))
+        _check(self.L, self._call("sample_rows")(ctypes.byref(self.net.desc), ctypes.byref(self._hp),
+                                                 _vp(self.block.data_ptr()), int(size), _vp(out.data_ptr()),
+                                                 _stream(self.block.device)))
         return out
 
     def check_errors(self):
@@ -1260,7 +1271,7 @@ class ConvDQNLearner:
         outside the fp16 split range (the learner's launches wait for nothing,
         so there is no timeout to report)."""
         if int(self.net.packed[-4].item()):
-            raise DroneRLError("drl_convnet_dqn_train: a learned weight left the f32 act's range (|w| >= 65504 or "
+            raise DroneRLError(f"{self._abi}_train: a learned weight left the f32 act's range (|w| >= 65504 or "
                                "not finite); the act's Q values are not valid")
 
     def save(self, path: str, format: str = "torch", **kw):
@@ -1277,8 +1288,8 @@ class ConvDQNLearner:
         the counters from zero (step 0, epsilon `epsilon` or
         hp.epsilon_start).  The online and target parameters are kept."""
         eps = self.hp.epsilon_start if epsilon is None else float(epsilon)
-        _check(self.L, self.L.drl_convnet_dqn_init(ctypes.byref(self.net.desc), self.hp.batch,
-                                                   _vp(self.block.data_ptr()), eps, _stream(self.block.device)))
+        _check(self.L, self._call("init")(ctypes.byref(self.net.desc), self.hp.batch,
+                                          _vp(self.block.data_ptr()), eps, _stream(self.block.device)))
 
     def counters(self) -> dict:
         """Host copy of the device counters (synchronises)."""
@@ -1286,3 +1297,22 @@ class ConvDQNLearner:
         d = self.block[self.layout.counters_off + 16:self.layout.counters_off + 32].view(torch.float64).cpu()
         return {"step": int(i[0]), "count": int(i[1]), "epsilon": float(f[2]), "loss": float(f[3]),
                 "beta1_pow": float(d[0]), "beta2_pow": float(d[1])}
+
+
+CONV_DQN_MAX_BATCH, CONV_DQN_LARGE_MAX_BATCH = 64, 4096  # drl_convnet_dqn_train's limit; DRL_CONVNET_DQN_LARGE_MAX_BATCH
+
+
+class LargeBatchConvDQNLearner(ConvDQNLearner):
+    """ConvDQNLearner for replay batches up to 4096 (train_jax.py
+    --network_type conv --batch_size beyond 64): the same agent block layout
+    for the four parameter sets and the counters, the same semantics and
+    surface, run by drl_convnet_dqn_large_train: the rows as ConvDQNLearner
+    computes them, each parameter's gradient as partial sums over chunks of 64
+    rows added in chunk order, Adam, the target blend, the counters and the
+    re-pack, a fixed chain of kernel launches with no synchronisation, so
+    `train` is graph-capturable and reproducible bit for bit.  At batch <= 64
+    (one chunk) both learners leave identical sets, counters, loss and packed
+    image.  The block grows with the batch: batch x layout.row_bytes of rows
+    plus ceil(batch / 64) x n_params x 4 bytes of partial gradients."""
+
+    _abi = "drl_convnet_dqn_large"

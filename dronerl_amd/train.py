@@ -51,14 +51,15 @@ def train(params: EnvParams, num_envs: int, num_steps: int, hidden: Sequence[int
     dqn.WideQNetwork trained by dqn.WideDQNLearner (one GPU only), otherwise
     today's QNetwork path.  hp.batch (--batch_size): 1..4096 for dense nets
     (dqn.make_learner: the single-launch learner up to 64, the large-batch
-    one above; a wide net: the launch chain at every batch), 1..64 for conv
-    nets.
+    one above; a wide net: the launch chain at every batch) and for conv nets
+    (dqn.ConvDQNLearner up to 64, dqn.LargeBatchConvDQNLearner above).
 
     network_type "conv" (train_jax.py --network_type conv): a ConvQNetwork
     of conv_layers (the reference's tuple of dicts; default train_jax.py's
     one 3x3 layer of 8 channels, padding 1) and conv_dense_layers on the
-    policy code, trained by dqn.ConvDQNLearner (drl_convnet_dqn_train) in the
-    same loop; `hidden` is then unused.  One GPU only (world == 1).
+    policy code, trained by dqn.make_learner's conv learner
+    (drl_convnet_dqn_train, or drl_convnet_dqn_large_train above batch 64) in
+    the same loop; `hidden` is then unused.  One GPU only (world == 1).
 
     world > 1 (one process per GPU, an initialised torch.distributed group):
     train_jax.py --use_sharding (:196-212) -- this rank steps envs
@@ -66,8 +67,7 @@ def train(params: EnvParams, num_envs: int, num_steps: int, hidden: Sequence[int
     replay ring is sharded (global_learner.ShardedReplay) and every rank runs
     the same learner; env_offset is then ignored.  The returned rate counts
     every rank's envs."""
-    from .dqn import (ConvDQNLearner, ConvQNetwork, DQNHParams, QNetwork, ReplayBuffer, WideQNetwork, is_wide,
-                      make_learner)
+    from .dqn import ConvQNetwork, DQNHParams, QNetwork, ReplayBuffer, WideQNetwork, is_wide, make_learner
     from .distributed import shard_envs
     from .env import BatchedDeliveryDrones
     from .global_learner import ShardedReplay
@@ -94,7 +94,8 @@ def train(params: EnvParams, num_envs: int, num_steps: int, hidden: Sequence[int
         net = ConvQNetwork((W, W, 6), conv_layers if conv_layers is not None else TRAIN_JAX_CONV_LAYERS,
                            tuple(conv_dense_layers), device=dev, generator=torch.Generator().manual_seed(seed),
                            input="code")
-        learner = ConvDQNLearner(net, hp, generator=torch.Generator().manual_seed(seed + 1))
+        # (batches up to 64: ConvDQNLearner; up to 4096: LargeBatchConvDQNLearner's chunked gradients)
+        learner = make_learner(net, hp, generator=torch.Generator().manual_seed(seed + 1))
     elif wide:  # (a width above 128: the wide act and the launch-chain learner, dqn.WideDQNLearner)
         net = WideQNetwork(D, tuple(hidden), device=dev, generator=torch.Generator().manual_seed(seed), input="code")
         learner = make_learner(net, hp, generator=torch.Generator().manual_seed(seed + 1))

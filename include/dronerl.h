@@ -502,7 +502,8 @@ int drl_qnet_act_eps(const drl_qnet_desc* d, const void* d_packed, const void* d
  * ------------------------------------------------------------------------ */
 typedef struct drl_dqn_hparams {
     int32_t batch;                  /* sample batch (train_jax.py --batch_size, 8): 1..64 for drl_dqn_train and
-                                       drl_convnet_dqn_train, 1..DRL_DQN_LARGE_MAX_BATCH for drl_dqn_large_train */
+                                       drl_convnet_dqn_train, 1..DRL_DQN_LARGE_MAX_BATCH (4096) for
+                                       drl_dqn_large_train and drl_convnet_dqn_large_train */
     int32_t target_update_interval; /* >= 1 (--target_update_interval, 10) */
     int32_t epsilon_decay_every;    /* >= 1 (--epsilon_decay_every, 5) */
     int32_t reserved;               /* 0 */
@@ -747,6 +748,48 @@ int drl_convnet_dqn_train(const drl_convnet_desc* d, const drl_dqn_hparams* h, v
 /* drl_dqn_sample_rows for this agent block. */
 int drl_convnet_dqn_sample_rows(const drl_convnet_desc* d, const drl_dqn_hparams* h, const void* d_agent,
                                 int64_t size, int64_t* d_slots, hipStream_t stream);
+
+/* ------------------------------------------------------------------------
+ * The same learner for replay batches up to DRL_CONVNET_DQN_LARGE_MAX_BATCH:
+ * the four calls of drl_convnet_dqn_* with the same arguments, the same
+ * drl_convnet_desc, drl_dqn_hparams, drl_dqn_counters, drl_replay, row kinds
+ * (f32 or policy code) and row draw, and the same drl_convnet_dqn_layout
+ * with a larger scratch.  One call is a fixed chain of stream-ordered kernel
+ * launches (rows: one workgroup per sampled row; the dense layers' and the
+ * conv layers' partial gradients per chunk of 64 rows; update; counters; the
+ * pack kernel): no workgroup waits for another, no float atomics, no memset,
+ * nothing allocated, no synchronisation; it can be captured into a graph,
+ * whose replays continue the schedule.  With size < batch only the target
+ * blend (when due) and the counters run.
+ * The reduction order is fixed: a row's forward, TD and backward are
+ * drl_convnet_dqn_train's, the head delta (d + d) / float(batch); rows are
+ * cut into chunks of 64 (chunk c: rows 64 c .. min(64 c + 63, batch - 1)) and
+ * a chunk's partial gradient of a parameter is summed exactly as
+ * drl_convnet_dqn_train sums its whole gradient; g = p[0] + p[1] + ... in
+ * chunk order, then Adam and the blend; the loss is the chunks' squared-error
+ * sums (rows in order) added in chunk order, / float(batch).  At batch <= 64
+ * there is one chunk and the call equals drl_convnet_dqn_train bit for bit
+ * (the four sets, the counters, the loss, the packed image).
+ * Limits, each refused by name before any device work: drl_convnet_desc's,
+ * batch in [1, DRL_CONVNET_DQN_LARGE_MAX_BATCH], a row's working set within
+ * DRL_CONVNET_DQN_ROW_BYTES_MAX.  The block's scratch holds 16 KB of squared
+ * errors, batch x row_bytes of rows and ceil(batch / 64) x n_params x 4 bytes
+ * of partial gradients (n_params rounded up to 4): a few hundred MB at the
+ * corners (batch 4096 with 64 KB rows: 256 MB of rows).
+ * ------------------------------------------------------------------------ */
+#define DRL_CONVNET_DQN_LARGE_MAX_BATCH 4096
+/* Host only (works without a device). */
+int drl_convnet_dqn_large_layout_query(const drl_convnet_desc* d, int32_t batch, drl_convnet_dqn_layout* layout);
+/* Zero the Adam moments and the counters, epsilon = epsilon_start.  The caller
+ * writes the online and target parameters.  Does not synchronise. */
+int drl_convnet_dqn_large_init(const drl_convnet_desc* d, int32_t batch, void* d_agent, float epsilon_start,
+                               hipStream_t stream);
+/* drl_convnet_dqn_train's arguments and result at batches up to 4096. */
+int drl_convnet_dqn_large_train(const drl_convnet_desc* d, const drl_dqn_hparams* h, void* d_agent, void* d_packed,
+                                const struct drl_replay* r, int64_t size, hipStream_t stream);
+/* drl_dqn_sample_rows for this agent block. */
+int drl_convnet_dqn_large_sample_rows(const drl_convnet_desc* d, const drl_dqn_hparams* h, const void* d_agent,
+                                      int64_t size, int64_t* d_slots, hipStream_t stream);
 
 /* ------------------------------------------------------------------------
  * Wide dense Q-networks: hidden widths up to DRL_WIDENET_MAX_WIDTH
