@@ -56,6 +56,8 @@ EXPORTS = ["drl_abi_version", "drl_last_error", "drl_side_from_density", "drl_la
            # dense nets with hidden widths up to 256 (dronerl_amd.dqn.WideQNetwork, WideDQNLearner)
            "drl_widenet_packed_bytes", "drl_widenet_pack", "drl_widenet_act", "drl_widenet_dqn_layout_query",
            "drl_widenet_dqn_init", "drl_widenet_dqn_train", "drl_widenet_dqn_sample_rows",
+           # multi-agent evaluation (dronerl_amd.evaluator)
+           "drl_obs_code_all", "drl_score_add",
            # measurement helper (the measured copy-kernel peak)
            "drl_hbm_probe"]
 
@@ -142,7 +144,10 @@ def lib():
     L.drl_encode.argtypes = [P, S, vp, vp, vp, vp, vp, vp]
     L.drl_synth_actions.argtypes = [u64, u64, i64, i64, i32, vp, vp]
     L.drl_hbm_probe.argtypes = [vp, vp, i64, i32, vp]
-    for f in ["drl_layout_query", "drl_reset", "drl_step", "drl_step_ex", "drl_rollout", "drl_refill", "drl_mt_get", "drl_mt_set", "drl_obs", "drl_grid_obs", "drl_decode", "drl_encode",
+    f64 = ctypes.c_double
+    L.drl_obs_code_all.argtypes = [P, S, vp, vp]
+    L.drl_score_add.argtypes = [vp, i64, i32, f64, f64, f64, f64, vp, vp]
+    for f in ["drl_obs_code_all", "drl_score_add","drl_layout_query", "drl_reset", "drl_step", "drl_step_ex", "drl_rollout", "drl_refill", "drl_mt_get", "drl_mt_set", "drl_obs", "drl_grid_obs", "drl_decode", "drl_encode",
               "drl_synth_actions", "drl_obs_code", "drl_step_code", "drl_code_decode", "drl_hbm_probe"]:
         getattr(L, f).restype = ctypes.c_int
     if L.drl_abi_version() != DRL_ABI_VERSION:

@@ -255,6 +255,24 @@ int drl_hbm_probe(const void* d_src, void* d_dst, int64_t bytes, int32_t mode, h
  * the code alone (k ignored). */
 int drl_obs_code(const drl_params* p, const drl_state* s, int32_t k, float* d_obs, void* d_code, hipStream_t stream);
 
+/* Multi-agent evaluation (drone_evaluator.py:97-204; dronerl_amd/evaluator.py): every drone driven by its own
+ * policy.
+ * drl_obs_code_all: the policy code of EVERY drone index of every env, d_codes u8
+ * [n_drones][E][drl_policy_code_bytes(window_radius)], drone-major, 16-B aligned.  Row (d, e) is bit for bit
+ * the row drl_obs_code writes for an env in which drone index d stands where index 0 does: the same u16 cell
+ * encoding, groups and zero padding, walls as DRL_SKYSCRAPER, centred on drone INDEX d (not dict slot d).
+ * Drone d's block is a contiguous run of code rows, so drl_qnet_act_code / drl_convnet_act / drl_widenet_act
+ * read it unchanged (d_actions + d, action_stride = n_drones).  Reads s->ground and s->drones only; num_envs
+ * must be >= 1. */
+int drl_obs_code_all(const drl_params* p, const drl_state* s, void* d_codes, hipStream_t stream);
+/* One step's rewards into running scores, in the reference's arithmetic (a float64 array += Python doubles):
+ * d_scores f64 [E][n_drones] += v, where v is the first of crash, charge, pickup, delivery whose f32 rounding
+ * equals the f32 reward d_rewards[e][d] (drl_step's output), else 0 for a zero reward, else the f32 widened.
+ * One f64 add per element per call, so a sequence of calls equals numpy's `scores += step_rewards` bit for
+ * bit. */
+int drl_score_add(const float* d_rewards, int64_t num_envs, int32_t n_drones, double crash_reward, double charge_reward,
+                  double pickup_reward, double delivery_reward, double* d_scores, hipStream_t stream);
+
 /* GridView observation (wrappers.py:10-31,34-43): the [side][side][6] f32
  * base grid of every env (each drone of an env sees the same grid):
  * d_grid f32 [E][side][side][6], channels as drl_obs, no wall padding. */
