@@ -56,6 +56,9 @@ EXPORTS = ["drl_abi_version", "drl_last_error", "drl_side_from_density", "drl_la
            # dense nets with hidden widths up to 256 (dronerl_amd.dqn.WideQNetwork, WideDQNLearner)
            "drl_widenet_packed_bytes", "drl_widenet_pack", "drl_widenet_act", "drl_widenet_dqn_layout_query",
            "drl_widenet_dqn_init", "drl_widenet_dqn_train", "drl_widenet_dqn_sample_rows",
+           # a population of dense DQN agents in one launch chain (dronerl_amd.population)
+           "drl_pop_layout_query", "drl_pop_init", "drl_pop_act", "drl_pop_replay_add", "drl_pop_train",
+           "drl_pop_sample_rows",
            # multi-agent evaluation (dronerl_amd.evaluator)
            "drl_obs_code_all", "drl_score_add",
            # measurement helper (the measured copy-kernel peak)

@@ -874,6 +874,85 @@ int drl_widenet_dqn_train(const drl_widenet_desc* d, const drl_dqn_hparams* h, v
 int drl_widenet_dqn_sample_rows(const drl_widenet_desc* d, const drl_dqn_hparams* h, const void* d_agent,
                                 int64_t size, int64_t* d_slots, hipStream_t stream);
 
+/* ------------------------------------------------------------------------
+ * A population of dense DQN agents (run_jax_sweep.py, torch_impl/sweep.py:
+ * many training runs that differ in their hyperparameters): `members`
+ * agents, each the learner block written above drl_dqn_train on its own
+ * envs, acting and learning in the same launches.  One step of the whole
+ * population is one chain of launches whose length does not depend on
+ * `members`; a member's arithmetic is drl_dqn_large_train's bit for bit and
+ * does not depend on which other members share the population.
+ *   Envs: one batch of members * E envs; member m owns envs m*E .. m*E+E-1.
+ *   Env seeding, drl_synth_actions and the exploration draw stay keyed on the
+ *   global env index, so member m is reproduced by a population of one whose
+ *   envs start at env_offset + m*E.
+ *   Shared: the net's architecture (a drl_widenet_desc with input
+ *   DRL_QNET_INPUT_CODE: a 5x5, 7x7 or 9x9 window, 1..3 hidden widths,
+ *   multiples of 8 in [8, DRL_WIDENET_MAX_WIDTH], 1..8 actions), E, the ring
+ *   capacity.  Per member (a drl_dqn_hparams each, uploaded once by
+ *   drl_pop_init): batch in [1, max_batch], gamma, learning_rate, the Adam
+ *   constants, tau, target_update_interval, the epsilon schedule,
+ *   sample_seed; and the initial parameters, which the caller writes.
+ * The block (device, caller-owned, 16-B aligned, drl_pop_layout.bytes):
+ * `members` agent blocks member_stride bytes apart, each laid out exactly as
+ * drl_dqn_large_layout_query / drl_widenet_dqn_layout_query lay out one agent
+ * at batch max_batch (`member`: four parameter sets, drl_dqn_counters,
+ * scratch), then the members' hyperparameter records at hparams_off.
+ * The rings: a drl_replay whose five arrays hold `members` rings of
+ * `capacity` rows each, ring m at row m * capacity; policy-code rows
+ * (obs_floats = drl_policy_code_bytes / 4).  The cursor and size are equal
+ * for every member and stay with the caller.
+ * No call but drl_pop_init synchronises or reads host hyperparameters;
+ * nothing is allocated, no workgroup waits for another, no float atomic is
+ * used: act, add and train are graph-capturable.  Every argument is
+ * validated before any device work.
+ * ------------------------------------------------------------------------ */
+#define DRL_POP_MAX_MEMBERS 1024
+typedef struct drl_pop_layout {
+    drl_dqn_layout member;   /* one member's block (offsets from the member's start) */
+    int64_t member_stride;   /* bytes from member m's block to member m+1's */
+    int64_t hparams_off;     /* bytes: the hyperparameter records (opaque) */
+    int64_t hparams_stride;
+    int64_t bytes;
+    int32_t members, max_batch;
+} drl_pop_layout;
+/* Host only. */
+int drl_pop_layout_query(const drl_widenet_desc* d, int32_t members, int32_t max_batch, drl_pop_layout* layout);
+/* h, epsilon_start: HOST arrays of `members` entries.  Uploads the records
+ * (synchronises `stream`), then zeroes every member's Adam moments and
+ * counters on the device, epsilon = epsilon_start[m].  The caller writes the
+ * online and target parameters. */
+int drl_pop_init(const drl_widenet_desc* d, int32_t members, int32_t max_batch, const drl_dqn_hparams* h,
+                 const float* epsilon_start, void* d_pop, hipStream_t stream);
+/* Drone 0's epsilon-greedy action of every env from its member's online f32
+ * parameters (d_code: [members * E] policy-code rows; epsilon: the member's
+ * device counter, or none with greedy != 0) into column 0 of d_actions
+ * [members * E][n_drones], and drl_synth_actions(synth_seed, synth_step,
+ * env_offset) into columns 1..n_drones-1.  The forward is f32 in the
+ * learner's order, so d_q (nullable, [members * E][n_actions]) equals the
+ * learner's own Q bit for bit (the MFMA acts agree with it to ~1e-5). */
+int drl_pop_act(const drl_widenet_desc* d, int32_t members, int32_t max_batch, const void* d_pop, const void* d_code,
+                int64_t envs_per_member, int32_t greedy, uint64_t seed, uint64_t step, int64_t env_offset,
+                int32_t* d_actions, int32_t n_drones, uint64_t synth_seed, uint64_t synth_step, float* d_q,
+                hipStream_t stream);
+/* drl_replay_add for every member: env m*E + i's drone-0 transition
+ * (d_code_prev row, d_actions / d_rewards / d_dones [members * E][n_drones]
+ * column 0, d_code row) lands in slot (cursor + i) % capacity of ring m; with
+ * E > capacity a member's last `capacity` envs are kept.  The caller advances
+ * cursor by E. */
+int drl_pop_replay_add(const drl_widenet_desc* d, int32_t members, const drl_replay* r, int64_t cursor,
+                       int64_t envs_per_member, const void* d_code_prev, const void* d_code, const int32_t* d_actions,
+                       const float* d_rewards, const uint8_t* d_dones, int32_t n_drones, hipStream_t stream);
+/* One learner step of every member on rings holding `size` rows each: member
+ * m trains iff size >= its batch (decided on the device); one that does not
+ * still blends its target when due, decays epsilon and advances its step. */
+int drl_pop_train(const drl_widenet_desc* d, int32_t members, int32_t max_batch, void* d_pop, const drl_replay* r,
+                  int64_t size, hipStream_t stream);
+/* d_slots int64 [members][max_batch]: the slots member m's next step draws in
+ * its first batch_m entries, -1 behind them. */
+int drl_pop_sample_rows(const drl_widenet_desc* d, int32_t members, int32_t max_batch, const void* d_pop, int64_t size,
+                        int64_t* d_slots, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
