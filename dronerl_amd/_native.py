@@ -59,6 +59,9 @@ EXPORTS = ["drl_abi_version", "drl_last_error", "drl_side_from_density", "drl_la
            # a population of dense DQN agents in one launch chain (dronerl_amd.population)
            "drl_pop_layout_query", "drl_pop_init", "drl_pop_act", "drl_pop_replay_add", "drl_pop_train",
            "drl_pop_sample_rows",
+           # a population of conv DQN agents in one launch chain (dronerl_amd.population.ConvPopulationDQN)
+           "drl_convpop_layout_query", "drl_convpop_init", "drl_convpop_act", "drl_convpop_train",
+           "drl_convpop_sample_rows",
            # multi-agent evaluation (dronerl_amd.evaluator)
            "drl_obs_code_all", "drl_score_add",
            # measurement helper (the measured copy-kernel peak)

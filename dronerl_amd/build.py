@@ -26,12 +26,16 @@ SOURCES = [os.path.join(CSRC, "dronerl_kernels.hip"), os.path.join(CSRC, "droner
            os.path.join(CSRC, "evalcode", "dronerl_evalcode.hip"),
            os.path.join(CSRC, "evalcode", "dronerl_evalcode_api.cpp"),
            os.path.join(CSRC, "population", "dronerl_population.hip"),
-           os.path.join(CSRC, "population", "dronerl_population_api.cpp")]
+           os.path.join(CSRC, "population", "dronerl_population_api.cpp"),
+           os.path.join(CSRC, "convpop", "dronerl_convpop.hip"),
+           os.path.join(CSRC, "convpop", "dronerl_convpop_api.cpp")]
 DEPS = SOURCES + [os.path.join(CSRC, "dronerl_internal.h"), os.path.join(CSRC, "dronerl_act_common.h"),
                   os.path.join(CSRC, "dronerl_learn_common.h"),
                   os.path.join(CSRC, "convlearn", "dronerl_convlearn_layout.h"),
                   os.path.join(CSRC, "convlearn", "dronerl_convlearn_rows.h"),
                   os.path.join(CSRC, "convlarge", "dronerl_convlarge_layout.h"),
+                  os.path.join(CSRC, "convlarge", "dronerl_convlarge_chain.h"),
+                  os.path.join(CSRC, "convpop", "dronerl_convpop_layout.h"),
                   os.path.join(CSRC, "largelearn", "dronerl_largelearn_layout.h"),
                   os.path.join(CSRC, "largelearn", "dronerl_largelearn_chain.h"),
                   os.path.join(CSRC, "population", "dronerl_population_layout.h"),

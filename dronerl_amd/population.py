@@ -1,5 +1,6 @@
-"""A population of dense DQN agents trained side by side on one GPU
-(include/dronerl.h drl_pop_*; dronerl_amd/csrc/population/).
+"""A population of DQN agents trained side by side on one GPU: dense nets
+(include/dronerl.h drl_pop_*; dronerl_amd/csrc/population/) or conv nets
+(drl_convpop_*; dronerl_amd/csrc/convpop/; ConvPopulationDQN).
 
 Reference: run_jax_sweep.py (1,000 train_jax.py runs that differ in
 num_envs, batch_size, learning_rate, epsilon_end and the net) and
@@ -28,8 +29,9 @@ from typing import Optional, Sequence
 import torch
 
 from ._native import DroneRLError, lib
-from .dqn import (INPUTS, NUM_ACTIONS, DQNHParams, DrlDqnHParams, DrlDqnLayout, DrlReplay, DrlWidenetDesc, QNetwork,
-                  WideQNetwork, _bind, _check, _on, _stream, _vp, flax_kernel_init, is_wide)
+from .dqn import (INPUTS, NUM_ACTIONS, ConvQNetwork, DQNHParams, DrlConvnetDesc, DrlConvnetDqnLayout, DrlDqnHParams,
+                  DrlDqnLayout, DrlReplay, DrlWidenetDesc, QNetwork, WideQNetwork, _bind, _bind_convnet, _check, _on,
+                  _stream, _vp, convnet_desc, flax_kernel_init, is_wide)
 from .params import EnvParams
 
 POP_MAX_MEMBERS = 1024  # DRL_POP_MAX_MEMBERS
@@ -319,6 +321,202 @@ class PopulationDQN:
         save_dense(path, ws, bs, (self.window, self.window, 6), format=format, **kw)
 
 
+class DrlConvPopLayout(ctypes.Structure):
+    _fields_ = [("member", DrlConvnetDqnLayout), ("member_stride", ctypes.c_int64), ("hparams_off", ctypes.c_int64),
+                ("hparams_stride", ctypes.c_int64), ("bytes", ctypes.c_int64), ("members", ctypes.c_int32),
+                ("max_batch", ctypes.c_int32)]
+
+
+def _bind_convpop(L):
+    if getattr(L, "_convpop_ready", False):
+        return L
+    i32, i64, u64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64
+    D, R = ctypes.POINTER(DrlConvnetDesc), ctypes.POINTER(DrlReplay)
+    sig = {
+        "drl_convpop_layout_query": [D, i32, i32, ctypes.POINTER(DrlConvPopLayout)],
+        "drl_convpop_init": [D, i32, i32, ctypes.POINTER(DrlDqnHParams), ctypes.POINTER(ctypes.c_float), _vp, _vp],
+        "drl_convpop_act": [D, i32, i32, _vp, _vp, i64, i32, u64, u64, i64, _vp, i32, u64, u64, _vp, _vp],
+        "drl_convpop_train": [D, i32, i32, _vp, R, i64, _vp],
+        "drl_convpop_sample_rows": [D, i32, i32, _vp, i64, _vp, _vp],
+    }
+    for name, args in sig.items():
+        f = getattr(L, name)
+        f.argtypes = args
+        f.restype = ctypes.c_int
+    L._convpop_ready = True
+    return L
+
+
+class ConvPopulationDQN(PopulationDQN):
+    """P conv DQN agents in one device allocation (drl_convpop_*;
+    dronerl_amd/csrc/convpop/): PopulationDQN's surface for a ConvQNetwork
+    architecture on the policy code.  Member m's block is laid out as
+    LargeBatchConvDQNLearner's at `max_batch`; its arithmetic is that
+    learner's bit for bit, whoever shares the population.
+
+    The act is an f32 forward by the learner's own per-layer code on the
+    member's online set (its Q is the learner's Q bit for bit; no packed image
+    exists and nothing is re-packed after a train step).  ConvQNetwork's MFMA
+    act agrees with it to ~1e-5, not bit for bit, so a member reproduces under
+    this API, not necessarily under `train()`.
+
+    obs_shape (W, W, 6) with W in 5, 7, 9; conv_layers / dense_layers as
+    ConvQNetwork takes them.  seeds: member m's online net from seeds[m], its
+    target net from seeds[m] + 1, as `train` initialises a conv agent; or
+    `online` / `target`: per member ([weights], [biases]) in forward order
+    (conv layers [out][in][k][k], then dense [out][in], the Q head last)."""
+
+    def __init__(self, obs_shape, conv_layers, dense_layers: Sequence[int], hps: Sequence[DQNHParams],
+                 envs_per_member: int, n_actions: int = NUM_ACTIONS, device=None,
+                 seeds: Optional[Sequence[int]] = None, max_batch: Optional[int] = None, online=None, target=None,
+                 guard_bytes: int = 0):
+        self.L = _bind_convpop(_bind_pop(_bind(_bind_convnet(lib()))))
+        self.hps = list(hps)
+        self.members = len(self.hps)
+        self.E = int(envs_per_member)
+        self.obs_shape = tuple(int(v) for v in obs_shape)
+        self.desc = convnet_desc(self.obs_shape, conv_layers, dense_layers, n_actions, "code")
+        self.conv_layers = tuple({"out_channels": int(c.out_channels), "kernel_size": int(c.kernel_size),
+                                  "stride": int(c.stride), "padding": int(c.padding)}
+                                 for c in self.desc.conv[:self.desc.n_conv])
+        self.dense_layers, self.n_actions = tuple(int(w) for w in dense_layers), int(n_actions)
+        self.max_batch = int(max_batch) if max_batch is not None else max([hp.batch for hp in self.hps] or [1])
+        lay = DrlConvPopLayout()
+        if self.L.drl_convpop_layout_query(ctypes.byref(self.desc), self.members, self.max_batch, ctypes.byref(lay)):
+            raise ValueError(self.L.drl_last_error().decode())
+        if self.E < 1:
+            raise ValueError("envs_per_member must be >= 1")
+        for m, hp in enumerate(self.hps):
+            if not 1 <= hp.batch <= self.max_batch:
+                raise ValueError(f"member {m}: batch must be in [1, max_batch={self.max_batch}]")
+        self.layout = lay
+        self.window = self.obs_shape[0]
+        self.in_features = self.window * self.window * 6
+        self.code_bytes = int(self.L.drl_policy_code_bytes((self.window - 1) // 2))
+        self.device = torch.device(device if device is not None else "cuda")
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self._alloc = torch.zeros(lay.bytes + int(guard_bytes), dtype=torch.uint8, device=self.device)
+        self.block = self._alloc[:lay.bytes]
+        self._f32 = self.block.view(torch.float32)
+        self.shapes, side, cin = [], self.window, 6
+        for c in self.conv_layers:
+            k, co = c["kernel_size"], c["out_channels"]
+            self.shapes.append(((co, cin, k, k), (co,)))
+            side, cin = (side + 2 * c["padding"] - k) // c["stride"] + 1, co
+        sizes = [side * side * cin, *self.dense_layers, self.n_actions]
+        self.shapes += [((sizes[i + 1], sizes[i]), (sizes[i + 1],)) for i in range(len(sizes) - 1)]
+        seeds = list(seeds) if seeds is not None else [0] * self.members
+        if len(seeds) != self.members:
+            raise ValueError("seeds: one per member")
+
+        def fresh(seed):  # (ConvQNetwork's own draw order: flax Conv / Dense lecun_normal, zero biases)
+            g = torch.Generator().manual_seed(int(seed))
+            return ([flax_kernel_init((ws[0], int(torch.Size(ws[1:]).numel())), 1.0, g).reshape(ws)
+                     for ws, _ in self.shapes], [torch.zeros(bs) for _, bs in self.shapes])
+
+        for m in range(self.members):
+            on = online[m] if online is not None else fresh(seeds[m])
+            tg = target[m] if target is not None else fresh(seeds[m] + 1)
+            for which, (ws, bs) in (("online", on), ("target", tg)):
+                if len(ws) != len(self.shapes) or len(bs) != len(self.shapes):
+                    raise ValueError(f"member {m} {which}: layer count mismatch")
+                for l, (w, b) in enumerate(self.params(which, m)):
+                    w.copy_(torch.as_tensor(ws[l]).to(self.device, torch.float32))
+                    b.copy_(torch.as_tensor(bs[l]).to(self.device, torch.float32))
+        self.epsilon = self._f32.as_strided((self.members,), (lay.member_stride // 4,),
+                                            (lay.member.counters_off + 8) // 4)
+        self._hp = (DrlDqnHParams * self.members)(*[hp.c() for hp in self.hps])
+        self.restart()
+
+    def restart(self):
+        """drl_convpop_init: every member's Adam moments and counters from
+        zero, epsilon = its epsilon_start; the parameters are kept."""
+        eps = (ctypes.c_float * self.members)(*[float(hp.epsilon_start) for hp in self.hps])
+        if self.L.drl_convpop_init(ctypes.byref(self.desc), self.members, self.max_batch, self._hp, eps,
+                                   _vp(self.block.data_ptr()), _stream(self.device)):
+            raise ValueError(self.L.drl_last_error().decode())
+
+    def params(self, which: str, m: int):
+        """[(W, b)] views of member m's parameter set ("online", "target",
+        "m", "v") in ConvDQNLearner.params' order and torch layouts."""
+        if which not in SETS:
+            raise ValueError(f"which must be one of {SETS}")
+        lay = self.layout.member
+        off = getattr(lay, which + "_off")
+        s = self.member_block(m)[off:off + 4 * lay.n_params].view(torch.float32)
+        out = []
+        for l, (ws, bs) in enumerate(self.shapes):
+            wo, bo = lay.weight_off[l], lay.bias_off[l]
+            out.append((s[wo:wo + int(torch.Size(ws).numel())].view(ws), s[bo:bo + bs[0]]))
+        return out
+
+    def act(self, code: torch.Tensor, step: int, seed: int = 0, env_offset: int = 0,
+            actions: Optional[torch.Tensor] = None, synth=(0, 0), greedy: bool = False,
+            q_out: Optional[torch.Tensor] = None, n_drones: int = 1) -> torch.Tensor:
+        """PopulationDQN.act's arguments and result (drl_convpop_act)."""
+        n = self.members * self.E
+        _on(code, self.device, torch.uint8, "code")
+        if tuple(code.shape) != (n, self.code_bytes) or not code.is_contiguous():
+            raise ValueError(f"code must be a contiguous uint8 [{n}, {self.code_bytes}] tensor")
+        if actions is None:
+            actions = torch.empty((n, n_drones), dtype=torch.int32, device=self.device)
+        _on(actions, self.device, torch.int32, "actions")
+        if actions.dim() != 2 or actions.shape[0] != n or not actions.is_contiguous():
+            raise ValueError(f"actions must be a contiguous int32 [{n}, n_drones] tensor")
+        if q_out is not None:
+            _on(q_out, self.device, torch.float32, "q_out")
+            if tuple(q_out.shape) != (n, self.n_actions) or not q_out.is_contiguous():
+                raise ValueError(f"q_out must be a contiguous float32 [{n}, {self.n_actions}] tensor")
+        _check(self.L, self.L.drl_convpop_act(
+            ctypes.byref(self.desc), self.members, self.max_batch, _vp(self.block.data_ptr()), _vp(code.data_ptr()),
+            self.E, int(bool(greedy)), seed & (2**64 - 1), int(step), int(env_offset), _vp(actions.data_ptr()),
+            actions.shape[1], synth[0] & (2**64 - 1), int(synth[1]),
+            None if q_out is None else _vp(q_out.data_ptr()), _stream(self.device)))
+        return actions
+
+    def train(self, replay: PopulationReplay):
+        """One learner block (train_jax.py:68-98, network_type conv) of every
+        member on its ring: member m trains iff replay.size >= its batch
+        (decided on the device)."""
+        if replay.obs.device != self.device or replay.members != self.members:
+            raise ValueError("the replay must be on the population's device and hold one ring per member")
+        _check(self.L, self.L.drl_convpop_train(ctypes.byref(self.desc), self.members, self.max_batch,
+                                                _vp(self.block.data_ptr()), ctypes.byref(replay._c), replay.size,
+                                                _stream(self.device)))
+
+    def sample_slots(self, size: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """PopulationDQN.sample_slots (drl_convpop_sample_rows)."""
+        if out is None:
+            out = torch.empty((self.members, self.max_batch), dtype=torch.int64, device=self.device)
+        _on(out, self.device, torch.int64, "out")
+        if tuple(out.shape) != (self.members, self.max_batch) or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous int64 [{self.members}, {self.max_batch}] tensor")
+        _check(self.L, self.L.drl_convpop_sample_rows(ctypes.byref(self.desc), self.members, self.max_batch,
+                                                      _vp(self.block.data_ptr()), int(size), _vp(out.data_ptr()),
+                                                      _stream(self.device)))
+        return out
+
+    def member_net(self, m: int, input: str = "obs"):
+        """A ConvQNetwork loaded with member m's online weights: what
+        train.evaluate and the line-up evaluator take."""
+        net = ConvQNetwork(self.obs_shape, self.conv_layers, self.dense_layers, n_actions=self.n_actions,
+                           device=self.device, input=input)
+        ws, bs = zip(*self.params("online", m))
+        nc = len(self.conv_layers)
+        net.load(ws[:nc], bs[:nc], ws[nc:], bs[nc:])
+        return net
+
+    def save(self, m: int, path: str, format: str = "torch", **kw):
+        """Member m's online net as train_jax.py:238-244 saves a trained conv
+        agent (checkpoint.save_conv)."""
+        from .checkpoint import save_conv
+        ws, bs = zip(*self.params("online", m))
+        nc = len(self.conv_layers)
+        kw.setdefault("conv_layers", self.conv_layers)
+        save_conv(path, ws[:nc], bs[:nc], ws[nc:], bs[nc:], self.obs_shape, format=format, **kw)
+
+
 @dataclass
 class PopulationResult:
     env: object
@@ -331,24 +529,36 @@ class PopulationResult:
 def train_population(params: EnvParams, members: Sequence[DQNHParams], envs_per_member: int, num_steps: int,
                      hidden: Sequence[int] = (128, 64), reset_env_every: int = 100, memory_size: int = 100_000,
                      seed: int = 0, env_offset: int = 0, action_seed: int = 2024, act_seed: int = 7, device=None,
-                     seeds: Optional[Sequence[int]] = None, on_step=None, **pop_kw) -> PopulationResult:
+                     seeds: Optional[Sequence[int]] = None, on_step=None, network_type: str = "dense",
+                     conv_layers=None, conv_dense_layers: Sequence[int] = (), **pop_kw) -> PopulationResult:
     """`train`'s loop for a population: per step the population act, one env
     step over all P*E envs writing drone 0's next policy code, the add into
     the members' rings, the members' learner blocks, and a reset of every env
     when step % reset_env_every == 0 (train_jax.py:99-113).  members: a
     DQNHParams each; seeds: each member's initialisation seed (default
     `seed` for all).  on_step(t, pop, replay, acts, rewards, dones): called
-    between step t's add and its train (tests)."""
+    between step t's add and its train (tests).  network_type "conv": a
+    ConvPopulationDQN of conv_layers (default train_jax.py's one 3x3 layer of
+    8 channels, padding 1) and conv_dense_layers; `hidden` is then unused."""
     from .env import BatchedDeliveryDrones
     if num_steps < 1 or reset_env_every < 1:
         raise ValueError("num_steps and reset_env_every must be >= 1")
+    if network_type not in ("dense", "conv"):
+        raise ValueError("network_type must be 'dense' or 'conv'")
     members = list(members)
     P, E = len(members), int(envs_per_member)
     env = BatchedDeliveryDrones(params, P * E, device=device, env_offset=env_offset)
     env.reset(seed=seed)
     dev, N, r = env.device, env.n_drones, params.window_radius
     D = (2 * r + 1) ** 2 * 6
-    pop = PopulationDQN(D, hidden, members, E, device=dev, seeds=seeds if seeds is not None else [seed] * P, **pop_kw)
+    seeds = seeds if seeds is not None else [seed] * P
+    if network_type == "conv":
+        from .checkpoint import TRAIN_JAX_CONV_LAYERS
+        W = 2 * r + 1
+        pop = ConvPopulationDQN((W, W, 6), conv_layers if conv_layers is not None else TRAIN_JAX_CONV_LAYERS,
+                                tuple(conv_dense_layers), members, E, device=dev, seeds=seeds, **pop_kw)
+    else:
+        pop = PopulationDQN(D, hidden, members, E, device=dev, seeds=seeds, **pop_kw)
     rb = PopulationReplay(P, memory_size, r, device=dev)
     code = [env.new_code(), env.new_code()]
     env.get_code(out=code[0])

@@ -953,6 +953,58 @@ int drl_pop_train(const drl_widenet_desc* d, int32_t members, int32_t max_batch,
 int drl_pop_sample_rows(const drl_widenet_desc* d, int32_t members, int32_t max_batch, const void* d_pop, int64_t size,
                         int64_t* d_slots, hipStream_t stream);
 
+/* ------------------------------------------------------------------------
+ * A population of conv DQN agents (run_jax_sweep.py draws network_type from
+ * ['dense', 'conv']): the five drl_pop_* calls above for a drl_convnet_desc
+ * with input DRL_QNET_INPUT_CODE (a 5x5, 7x7 or 9x9 window; every other
+ * limit is drl_convnet_dqn_large_*'s).  Each member is the learner block
+ * written above drl_convnet_dqn_train on its own envs; a member's arithmetic
+ * is drl_convnet_dqn_large_train's bit for bit and does not depend on which
+ * other members share the population; one step of all members is one chain
+ * of launches whose length does not depend on `members` (rows, the dense and
+ * the conv layers' chunk partials, update, counters).
+ *   Envs, what is shared and what a member owns: as for drl_pop_*.
+ *   The block: `members` agent blocks member_stride bytes apart, each laid
+ *   out exactly as drl_convnet_dqn_large_layout_query lays out one agent at
+ *   batch max_batch, then the hyperparameter records at hparams_off.
+ *   The rings: drl_pop_replay_add's, unchanged (it reads the window alone of
+ *   its description: pass a drl_widenet_desc with in_features = W*W*6).
+ *   The act is an f32 forward on the member's online set by the learner's
+ *   own per-layer code, one workgroup per env: its Q is the learner's Q bit
+ *   for bit.  There is no packed image and nothing is re-packed after a
+ *   train step.  drl_convnet_act (MFMA) agrees with it to ~1e-5, not bit for
+ *   bit: a member reproduces under this API, not necessarily under the
+ *   single-agent calls.
+ * No call but drl_convpop_init synchronises or reads host hyperparameters;
+ * nothing is allocated, no workgroup waits for another, no float atomic is
+ * used: act and train are graph-capturable.  Every argument is validated
+ * before any device work.
+ * ------------------------------------------------------------------------ */
+typedef struct drl_convpop_layout {
+    drl_convnet_dqn_layout member; /* one member's block (offsets from the member's start) */
+    int64_t member_stride;         /* bytes from member m's block to member m+1's */
+    int64_t hparams_off;           /* bytes: the hyperparameter records (opaque) */
+    int64_t hparams_stride;
+    int64_t bytes;
+    int32_t members, max_batch;    /* 1..DRL_POP_MAX_MEMBERS; 1..DRL_CONVNET_DQN_LARGE_MAX_BATCH */
+} drl_convpop_layout;
+/* Host only. */
+int drl_convpop_layout_query(const drl_convnet_desc* d, int32_t members, int32_t max_batch, drl_convpop_layout* layout);
+/* drl_pop_init's arguments and effects (the only call that synchronises). */
+int drl_convpop_init(const drl_convnet_desc* d, int32_t members, int32_t max_batch, const drl_dqn_hparams* h,
+                     const float* epsilon_start, void* d_pop, hipStream_t stream);
+/* drl_pop_act's arguments and rule. */
+int drl_convpop_act(const drl_convnet_desc* d, int32_t members, int32_t max_batch, const void* d_pop, const void* d_code,
+                    int64_t envs_per_member, int32_t greedy, uint64_t seed, uint64_t step, int64_t env_offset,
+                    int32_t* d_actions, int32_t n_drones, uint64_t synth_seed, uint64_t synth_step, float* d_q,
+                    hipStream_t stream);
+/* drl_pop_train's arguments and rule. */
+int drl_convpop_train(const drl_convnet_desc* d, int32_t members, int32_t max_batch, void* d_pop, const drl_replay* r,
+                      int64_t size, hipStream_t stream);
+/* drl_pop_sample_rows' arguments and result. */
+int drl_convpop_sample_rows(const drl_convnet_desc* d, int32_t members, int32_t max_batch, const void* d_pop,
+                            int64_t size, int64_t* d_slots, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
