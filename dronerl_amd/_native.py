@@ -62,6 +62,8 @@ EXPORTS = ["drl_abi_version", "drl_last_error", "drl_side_from_density", "drl_la
            # a population of conv DQN agents in one launch chain (dronerl_amd.population.ConvPopulationDQN)
            "drl_convpop_layout_query", "drl_convpop_init", "drl_convpop_act", "drl_convpop_train",
            "drl_convpop_sample_rows",
+           # a league: K learners sharing their envs, learner k on drone k (dronerl_amd.league)
+           "drl_league_act_plan_query", "drl_league_act", "drl_league_replay_add",
            # multi-agent evaluation (dronerl_amd.evaluator)
            "drl_obs_code_all", "drl_score_add",
            # measurement helper (the measured copy-kernel peak)

@@ -1005,6 +1005,53 @@ int drl_convpop_train(const drl_convnet_desc* d, int32_t members, int32_t max_ba
 int drl_convpop_sample_rows(const drl_convnet_desc* d, int32_t members, int32_t max_batch, const void* d_pop,
                             int64_t size, int64_t* d_slots, hipStream_t stream);
 
+/* ------------------------------------------------------------------------
+ * A league (torch_impl/helpers/rl_helpers.py MultiAgentTrainer.train): K
+ * learners that share ONE batch of E envs, learner k driving drone INDEX k
+ * of every env and learning from that drone's transitions.  Each learner is
+ * exactly a population member: the block is drl_pop_layout_query's with
+ * members = K, initialised by drl_pop_init, trained by drl_pop_train and
+ * sampled by drl_pop_sample_rows, all unchanged; the rings are the
+ * population's (K rings of `capacity` policy-code rows, ring k at row
+ * k * capacity, one cursor and size for all, advanced by E per step).
+ * 1 <= members <= min(n_drones, DRL_POP_MAX_MEMBERS).  Drones K..N-1 are the
+ * caller's (drl_synth_actions, or fixed nets through the code acts).
+ * The codes are drl_obs_code_all's output, [n_drones][E][code bytes]; learner
+ * k reads block k.  Neither call allocates or synchronises; no workgroup
+ * waits for another and no float atomic is used: both are graph-capturable.
+ * Every argument is validated before any device work.
+ * ------------------------------------------------------------------------ */
+typedef struct drl_league_act_plan {
+    int32_t env_tile;    /* envs of one learner a workgroup takes through every layer */
+    int32_t threads;     /* its size */
+    int32_t pass_units;  /* units of a layer it computes per pass over the inputs */
+    int32_t chunk_k;     /* input columns of a staged weight chunk */
+    int32_t ldx, lda;    /* LDS row strides (floats): decoded inputs, activations */
+    int32_t lds_bytes;   /* dynamic LDS of the launch */
+    int32_t lds_limit;   /* what lds_bytes stays within (a CU's 160 KiB) */
+} drl_league_act_plan;
+/* Host only: the act's tiling for a population description. */
+int drl_league_act_plan_query(const drl_widenet_desc* d, drl_league_act_plan* plan);
+/* Learner k's epsilon-greedy action of env i from its online f32 parameters
+ * on d_codes block k, into d_actions[i * n_drones + k] for k < members and NO
+ * other column.  The exploration draw is the population's with the stream
+ * seed + k (mod 2^64): explore_draw(seed + k, step, env_offset + i,
+ * n_actions, epsilon_k), epsilon_k the learner's device counter, or none with
+ * greedy != 0; with k = 0 this is drl_pop_act's stream.  The forward is f32
+ * in the learner's order (four partial sums over k mod 4, (s0 + s1) +
+ * (s2 + s3), + bias, nothing contracted), so d_q (nullable, [members][E]
+ * [n_actions]) equals the learner's own Q bit for bit. */
+int drl_league_act(const drl_widenet_desc* d, int32_t members, int32_t max_batch, const void* d_pop,
+                   const void* d_codes, int64_t num_envs, int32_t greedy, uint64_t seed, uint64_t step,
+                   int64_t env_offset, int32_t* d_actions, int32_t n_drones, float* d_q, hipStream_t stream);
+/* Ring k, slot (cursor + i) % capacity, receives d_codes_prev[k][i],
+ * d_actions / d_rewards / d_dones [i][k] and d_codes[k][i]; with E > capacity
+ * the last `capacity` envs are kept (drl_pop_replay_add's rule).  The caller
+ * advances cursor by E. */
+int drl_league_replay_add(const drl_widenet_desc* d, int32_t members, const drl_replay* r, int64_t cursor,
+                          int64_t num_envs, const void* d_codes_prev, const void* d_codes, const int32_t* d_actions,
+                          const float* d_rewards, const uint8_t* d_dones, int32_t n_drones, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
