@@ -30,7 +30,9 @@ SOURCES = [os.path.join(CSRC, "dronerl_kernels.hip"), os.path.join(CSRC, "droner
            os.path.join(CSRC, "convpop", "dronerl_convpop.hip"),
            os.path.join(CSRC, "convpop", "dronerl_convpop_api.cpp"),
            os.path.join(CSRC, "league", "dronerl_league.hip"),
-           os.path.join(CSRC, "league", "dronerl_league_api.cpp")]
+           os.path.join(CSRC, "league", "dronerl_league_api.cpp"),
+           os.path.join(CSRC, "convleague", "dronerl_convleague.hip"),
+           os.path.join(CSRC, "convleague", "dronerl_convleague_api.cpp")]
 DEPS = SOURCES + [os.path.join(CSRC, "dronerl_internal.h"), os.path.join(CSRC, "dronerl_act_common.h"),
                   os.path.join(CSRC, "dronerl_learn_common.h"),
                   os.path.join(CSRC, "convlearn", "dronerl_convlearn_layout.h"),
@@ -42,6 +44,7 @@ DEPS = SOURCES + [os.path.join(CSRC, "dronerl_internal.h"), os.path.join(CSRC, "
                   os.path.join(CSRC, "largelearn", "dronerl_largelearn_chain.h"),
                   os.path.join(CSRC, "population", "dronerl_population_layout.h"),
                   os.path.join(CSRC, "league", "dronerl_league_layout.h"),
+                  os.path.join(CSRC, "convleague", "dronerl_convleague_layout.h"),
                   os.path.join(CSRC, "widenet", "dronerl_widenet_layout.h"),
                   os.path.join(CSRC, "evalcode", "dronerl_evalcode_layout.h"),
                   os.path.join(CSRC, "convnet", "dronerl_convnet_layout.h"), os.path.join(REPO, "include", "dronerl.h")]

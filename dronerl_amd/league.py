@@ -22,6 +22,12 @@ explore_draw(seed + k, step, env_offset + i, n_actions, epsilon_k): with
 k = 0 the population's stream, so a league of one learner with the other
 drones random is `train_population` with one member, bit for bit.
 
+Conv learners (`ConvLeagueDQN`, train_league(network_type="conv"),
+`python -m dronerl_amd.conv_league`): each learner is a ConvPopulationDQN
+member and everything above holds with the conv population in the dense
+one's place; the act is drl_convleague_act (dronerl_amd/csrc/convleague/).
+One architecture per league: dense and conv learners do not mix.
+
     train_league(params, learners, num_envs, num_steps, opponents={4: path}) -> LeagueResult
     evaluate_league(result)                                     -> the greedy table
     python -m dronerl_amd.league --learners 2 --opponents a.safetensors b.safetensors ...
@@ -38,7 +44,7 @@ import torch
 
 from .dqn import DQNHParams, DrlReplay, DrlWidenetDesc, _check, _on, _stream, _vp
 from .params import EnvParams
-from .population import PopulationDQN, PopulationReplay, _bind_pop
+from .population import ConvPopulationDQN, PopulationDQN, PopulationReplay, _bind_pop
 
 U64 = 2 ** 64 - 1
 
@@ -164,6 +170,85 @@ class LeagueDQN(PopulationDQN):
         return actions
 
 
+class DrlConvLeagueActPlan(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("env_tile", "threads", "row_words", "lds_bytes", "lds_limit")]
+
+
+def _bind_convleague(L):
+    if getattr(L, "_convleague_ready", False):
+        return L
+    from .dqn import DrlConvnetDesc
+    _bind_league(L)
+    i32, i64, u64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64
+    D = ctypes.POINTER(DrlConvnetDesc)
+    sig = {
+        "drl_convleague_act_plan_query": [D, ctypes.POINTER(DrlConvLeagueActPlan)],
+        "drl_convleague_act": [D, i32, i32, _vp, _vp, i64, i32, u64, u64, i64, _vp, i32, _vp, _vp],
+    }
+    for name, args in sig.items():
+        f = getattr(L, name)
+        f.argtypes = args
+        f.restype = ctypes.c_int
+    L._convleague_ready = True
+    return L
+
+
+def conv_act_plan(desc) -> dict:
+    """The conv league act's tiling for a conv population description
+    (drl_convleague_act_plan_query): env_tile, threads, the LDS words of an
+    env's forward-only row, the launch's LDS bytes and their limit."""
+    from ._native import lib
+    from .dqn import _bind
+    L = _bind_convleague(_bind(lib()))
+    p = DrlConvLeagueActPlan()
+    if L.drl_convleague_act_plan_query(ctypes.byref(desc), ctypes.byref(p)):
+        raise ValueError(L.drl_last_error().decode())
+    return {n: int(getattr(p, n)) for n, _ in DrlConvLeagueActPlan._fields_}
+
+
+class ConvLeagueDQN(ConvPopulationDQN):
+    """K conv learners over the same E envs, learner k on drone index k: a
+    ConvPopulationDQN with members = K and envs_per_member = E whose act is
+    LeagueDQN.act's (drl_convleague_act: block k of every drone's code in,
+    column k of the action matrix out, T envs of a learner per workgroup so
+    that a fetched weight serves them all).  Its Q is drl_convpop_act's bit
+    for bit.  `train`, `member_net`, `save`, `params`, `counters` and
+    `sample_slots` are the conv population's."""
+
+    def __init__(self, obs_shape, conv_layers, dense_layers: Sequence[int], hps: Sequence[DQNHParams],
+                 num_envs: int, **kw):
+        super().__init__(obs_shape, conv_layers, dense_layers, hps, num_envs, **kw)
+        _bind_convleague(self.L)
+
+    @property
+    def act_plan(self) -> dict:
+        return conv_act_plan(self.desc)
+
+    def act(self, codes: torch.Tensor, step: int, seed: int = 0, env_offset: int = 0,
+            actions: Optional[torch.Tensor] = None, greedy: bool = False,
+            q: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """LeagueDQN.act's arguments, checks and result."""
+        K, E = self.members, self.E
+        _on(codes, self.device, torch.uint8, "codes")
+        if codes.dim() != 3 or tuple(codes.shape[1:]) != (E, self.code_bytes) or not codes.is_contiguous():
+            raise ValueError(f"codes must be a contiguous uint8 [n_drones, {E}, {self.code_bytes}] tensor")
+        N = int(codes.shape[0])
+        if actions is None:
+            actions = torch.zeros((E, N), dtype=torch.int32, device=self.device)
+        _on(actions, self.device, torch.int32, "actions")
+        if tuple(actions.shape) != (E, N) or not actions.is_contiguous():
+            raise ValueError(f"actions must be a contiguous int32 [{E}, {N}] tensor")
+        if q is not None:
+            _on(q, self.device, torch.float32, "q")
+            if tuple(q.shape) != (K, E, self.n_actions) or not q.is_contiguous():
+                raise ValueError(f"q must be a contiguous float32 [{K}, {E}, {self.n_actions}] tensor")
+        _check(self.L, self.L.drl_convleague_act(
+            ctypes.byref(self.desc), K, self.max_batch, _vp(self.block.data_ptr()), _vp(codes.data_ptr()), E,
+            int(bool(greedy)), int(seed) & U64, int(step), int(env_offset), _vp(actions.data_ptr()), N,
+            None if q is None else _vp(q.data_ptr()), _stream(self.device)))
+        return actions
+
+
 def resolve_opponents(opponents, learners: int, params: EnvParams, device=None) -> Dict[int, object]:
     """{drone index: device net} for the fixed opponents; an index that is
     missing or maps to None is a random drone.  A path is loaded as the
@@ -265,7 +350,8 @@ def train_league(params: EnvParams, learners: Sequence[DQNHParams], num_envs: in
                  hidden: Sequence[int] = (128, 64), opponents=None, reset_env_every: int = 100,
                  memory_size: int = 100_000, seed: int = 0, env_offset: int = 0, action_seed: int = 2024,
                  act_seed: int = 7, seeds: Optional[Sequence[int]] = None, on_step=None,
-                 device=None) -> LeagueResult:
+                 device=None, network_type: str = "dense", conv_layers=None,
+                 conv_dense_layers: Sequence[int] = ()) -> LeagueResult:
     """MultiAgentTrainer.train on the device: per step the synthetic columns,
     the league act (columns 0..K-1), the fixed opponents' greedy acts, one env
     step, every drone's next code, the add into the learners' rings, the
@@ -274,10 +360,16 @@ def train_league(params: EnvParams, learners: Sequence[DQNHParams], num_envs: in
     DQNHParams each; opponents: {drone index >= K: net | checkpoint path |
     None}, missing indices are random; seeds: each learner's initialisation
     seed (default `seed` for all).  on_step(t, league, replay, actions,
-    rewards, dones): called between step t's add and its train (tests)."""
+    rewards, dones): called between step t's add and its train (tests).
+    network_type "conv": every learner a conv net (a ConvLeagueDQN of
+    conv_layers, default train_jax.py's one 3x3 layer of 8 channels, padding
+    1, and conv_dense_layers; `hidden` is then unused), as train_population
+    takes them."""
     from .env import BatchedDeliveryDrones
     if num_steps < 1 or reset_env_every < 1:
         raise ValueError("num_steps and reset_env_every must be >= 1")
+    if network_type not in ("dense", "conv"):
+        raise ValueError("network_type must be 'dense' or 'conv'")
     learners = list(learners)
     K, E, N = len(learners), int(num_envs), params.n_drones
     if not 1 <= K <= N:
@@ -287,8 +379,14 @@ def train_league(params: EnvParams, learners: Sequence[DQNHParams], num_envs: in
     env.reset(seed=seed)
     dev = env.device
     opp = resolve_opponents(opponents, K, params, dev)
-    league = LeagueDQN((2 * r + 1) ** 2 * 6, hidden, learners, E, device=dev,
-                       seeds=seeds if seeds is not None else [seed] * K)
+    seeds = seeds if seeds is not None else [seed] * K
+    if network_type == "conv":
+        from .checkpoint import TRAIN_JAX_CONV_LAYERS
+        W = 2 * r + 1
+        league = ConvLeagueDQN((W, W, 6), conv_layers if conv_layers is not None else TRAIN_JAX_CONV_LAYERS,
+                               tuple(conv_dense_layers), learners, E, device=dev, seeds=seeds)
+    else:
+        league = LeagueDQN((2 * r + 1) ** 2 * 6, hidden, learners, E, device=dev, seeds=seeds)
     rb = LeagueReplay(K, memory_size, r, device=dev)
     loop = LeagueLoop(env, league, rb, opp, action_seed=action_seed, act_seed=act_seed)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -338,8 +436,8 @@ def evaluate_league(result_or_nets, params: Optional[EnvParams] = None, opponent
 
 
 # ------------------------------------------------------------ command line --
-CONV_LEARNERS_REFUSAL = ("--network_type conv: a league's learners are dense nets (conv learners are not "
-                         "implemented yet; conv checkpoints work as --opponents)")
+CONV_LEARNERS_REFUSAL = ("--network_type conv: a league's learners are dense nets (conv learners train with "
+                         "python -m dronerl_amd.conv_league; conv checkpoints work as --opponents)")
 SHARDING_REFUSAL = "a league runs on one GPU (no --use_sharding): sharded leagues are not implemented"
 
 

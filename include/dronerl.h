@@ -1052,6 +1052,40 @@ int drl_league_replay_add(const drl_widenet_desc* d, int32_t members, const drl_
                           int64_t num_envs, const void* d_codes_prev, const void* d_codes, const int32_t* d_actions,
                           const float* d_rewards, const uint8_t* d_dones, int32_t n_drones, hipStream_t stream);
 
+/* ------------------------------------------------------------------------
+ * A league of conv learners: the same league with every learner a member of a
+ * drl_convpop_layout block (members = K), initialised by drl_convpop_init,
+ * trained by drl_convpop_train and sampled by drl_convpop_sample_rows, all
+ * unchanged; the rings are the population's and drl_league_replay_add feeds
+ * them (it reads the code window and the member count of its description
+ * alone).  Only the act is new: drl_convpop_act's workgroup takes one env and
+ * fetches the member's weights once per env; a league has few learners with
+ * thousands of envs each, so here a workgroup takes env_tile envs of one
+ * learner through every layer and each weight word it fetches serves them all.
+ * The call neither allocates nor synchronises; no workgroup waits for another
+ * and no float atomic is used: it is graph-capturable.  Every argument is
+ * validated before any device work.
+ * ------------------------------------------------------------------------ */
+typedef struct drl_convleague_act_plan {
+    int32_t env_tile;   /* envs of one learner a workgroup takes through every layer (16, 8, 4 or 2) */
+    int32_t threads;    /* its size */
+    int32_t row_words;  /* LDS words of an env's forward-only row: input, every layer's output */
+    int32_t lds_bytes;  /* dynamic LDS of the launch: env_tile * row_words * 4 */
+    int32_t lds_limit;  /* what lds_bytes stays within (a CU's 160 KiB) */
+} drl_convleague_act_plan;
+/* Host only: the act's tiling for a conv population description. */
+int drl_convleague_act_plan_query(const drl_convnet_desc* d, drl_convleague_act_plan* plan);
+/* drl_league_act's arguments, rule and streams for a conv population block:
+ * learner k's action of env i into d_actions[i * n_drones + k] for k < members
+ * and NO other column, its draw explore_draw(seed + k, step, env_offset + i,
+ * n_actions, epsilon_k).  The forward is the conv learner's own per-row
+ * forward (drl_convpop_act's: taps in (ci, ky, kx) order, a dense unit's 64
+ * partial sums and xor tree, nothing contracted), so d_q (nullable,
+ * [members][E][n_actions]) equals drl_convpop_act's Q bit for bit. */
+int drl_convleague_act(const drl_convnet_desc* d, int32_t members, int32_t max_batch, const void* d_pop,
+                       const void* d_codes, int64_t num_envs, int32_t greedy, uint64_t seed, uint64_t step,
+                       int64_t env_offset, int32_t* d_actions, int32_t n_drones, float* d_q, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
