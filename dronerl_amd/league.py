@@ -319,6 +319,11 @@ class LeagueLoop:
                   0.0, actions=col)
         return self.actions
 
+    def add(self, nxt: torch.Tensor):
+        """The step's transitions (the codes the act read, `nxt` after the
+        env step) into the learners' rings."""
+        self.replay.add(self.codes[self.cur], self.actions, self.rewards, nxt, self.dones)
+
     def step(self, t: int, on_step=None, reset: bool = False):
         from .evaluator import obs_code_all
         env = self.env
@@ -326,7 +331,7 @@ class LeagueLoop:
         env.step(self.actions, rewards=self.rewards, dones=self.dones)
         nxt = self.codes[1 - self.cur]
         obs_code_all(env, nxt)
-        self.replay.add(self.codes[self.cur], self.actions, self.rewards, nxt, self.dones)
+        self.add(nxt)
         if on_step is not None:
             on_step(t, self.league, self.replay, self.actions, self.rewards, self.dones)
         self.league.train(self.replay)

@@ -1086,6 +1086,48 @@ int drl_convleague_act(const drl_convnet_desc* d, int32_t members, int32_t max_b
                        const void* d_codes, int64_t num_envs, int32_t greedy, uint64_t seed, uint64_t step,
                        int64_t env_offset, int32_t* d_actions, int32_t n_drones, float* d_q, hipStream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Shared-policy self-play (MultiAgentTrainer.train with one agent object
+ * under several keys of its `agents` dict): K learners that share ONE batch
+ * of E envs, learner k driving the `team` drone indices drones[k][0..team-1]
+ * of every env and learning from all of their transitions into its one ring.
+ * `drones` is a HOST array [members][team] of distinct indices in
+ * [0, n_drones), members * team <= n_drones; it travels to the kernels by
+ * value.  Each learner is exactly a population member, as in the league: the
+ * block, drl_pop_init, drl_pop_train and drl_pop_sample_rows are unchanged,
+ * the rings are the population's (one cursor and size for all, advanced by
+ * team * E per step: every learner drives the same number of drones).
+ * Drones in no team are the caller's.  A learner's rows are its team * E
+ * (drone, env) pairs taken slot-major, r = j * E + i.  The act's tiling is
+ * drl_league_act_plan_query's with a tile of env_tile consecutive rows r.
+ * Neither call reads device memory on the host, allocates or synchronises;
+ * no workgroup waits for another and no float atomic is used: both are
+ * graph-capturable.  Every argument is validated before any device work.
+ * ------------------------------------------------------------------------ */
+/* For learner k, team slot j and env i, with dr = drones[k][j]: the
+ * epsilon-greedy action from the learner's online f32 parameters on
+ * d_codes[dr][i], into d_actions[i * n_drones + dr] and NO column outside the
+ * teams.  The draw is explore_draw(seed + dr, step, env_offset + i,
+ * n_actions, epsilon_k), epsilon_k the learner's device counter, or none with
+ * greedy != 0: the stream is keyed on the drone index, so two drones of a
+ * team never share one.  The forward is drl_league_act's (four partial sums
+ * over k mod 4, (s0 + s1) + (s2 + s3), + bias, nothing contracted); d_q is
+ * nullable, [members][team][E][n_actions].  With team = 1 and
+ * drones[k][0] = k the actions and d_q are drl_league_act's byte for byte. */
+int drl_selfplay_act(const drl_widenet_desc* d, int32_t members, int32_t max_batch, const void* d_pop,
+                     const void* d_codes, int64_t num_envs, const int32_t* drones /* HOST [members][team] */,
+                     int32_t team, int32_t greedy, uint64_t seed, uint64_t step, int64_t env_offset,
+                     int32_t* d_actions, int32_t n_drones, float* d_q, hipStream_t stream);
+/* Ring k, slot (cursor + j * E + i) % capacity, receives d_codes_prev[dr][i],
+ * d_actions / d_rewards / d_dones [i][dr] and d_codes[dr][i]; with
+ * team * E > capacity only the rows with j * E + i >= team * E - capacity are
+ * stored (ReplayBuffer.add_many on the team's rows taken slot-major).  The
+ * caller advances cursor by team * E. */
+int drl_selfplay_replay_add(const drl_widenet_desc* d, int32_t members, const drl_replay* r, int64_t cursor,
+                            int64_t num_envs, const int32_t* drones, int32_t team, const void* d_codes_prev,
+                            const void* d_codes, const int32_t* d_actions, const float* d_rewards,
+                            const uint8_t* d_dones, int32_t n_drones, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
