@@ -27,7 +27,8 @@ SRCS := $(CSRC)/dronerl_kernels.hip $(CSRC)/dronerl_api.cpp $(CSRC)/dronerl_env.
         $(CSRC)/convpop/dronerl_convpop_api.cpp $(CSRC)/league/dronerl_league.hip \
         $(CSRC)/league/dronerl_league_api.cpp $(CSRC)/convleague/dronerl_convleague.hip \
         $(CSRC)/convleague/dronerl_convleague_api.cpp $(CSRC)/selfplay/dronerl_selfplay.hip \
-        $(CSRC)/selfplay/dronerl_selfplay_api.cpp
+        $(CSRC)/selfplay/dronerl_selfplay_api.cpp $(CSRC)/convselfplay/dronerl_convselfplay.hip \
+        $(CSRC)/convselfplay/dronerl_convselfplay_api.cpp
 DEPS := $(SRCS) $(CSRC)/dronerl_internal.h $(CSRC)/dronerl_act_common.h $(CSRC)/convnet/dronerl_convnet_layout.h \
         $(CSRC)/dronerl_learn_common.h $(CSRC)/convlearn/dronerl_convlearn_layout.h \
         $(CSRC)/largelearn/dronerl_largelearn_layout.h $(CSRC)/widenet/dronerl_widenet_layout.h \
@@ -35,7 +36,8 @@ DEPS := $(SRCS) $(CSRC)/dronerl_internal.h $(CSRC)/dronerl_act_common.h $(CSRC)/
         $(CSRC)/population/dronerl_population_layout.h $(CSRC)/convlearn/dronerl_convlearn_rows.h \
         $(CSRC)/convlarge/dronerl_convlarge_layout.h $(CSRC)/convlarge/dronerl_convlarge_chain.h \
         $(CSRC)/convpop/dronerl_convpop_layout.h $(CSRC)/league/dronerl_league_layout.h \
-        $(CSRC)/convleague/dronerl_convleague_layout.h $(CSRC)/selfplay/dronerl_selfplay_layout.h include/dronerl.h
+        $(CSRC)/convleague/dronerl_convleague_layout.h $(CSRC)/selfplay/dronerl_selfplay_layout.h \
+        $(CSRC)/convleague/dronerl_convleague_tile.h $(CSRC)/convselfplay/dronerl_convselfplay_layout.h include/dronerl.h
 
 asan: build/asan/liboracle.so build/asan/libdronerl.so
 

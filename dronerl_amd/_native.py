@@ -68,6 +68,8 @@ EXPORTS = ["drl_abi_version", "drl_last_error", "drl_side_from_density", "drl_la
            "drl_convleague_act_plan_query", "drl_convleague_act",
            # shared-policy self-play: a learner drives a team of drones (dronerl_amd.selfplay)
            "drl_selfplay_act", "drl_selfplay_replay_add",
+           # ... with conv learners (dronerl_amd.selfplay.ConvSelfPlayDQN)
+           "drl_convselfplay_act",
            # multi-agent evaluation (dronerl_amd.evaluator)
            "drl_obs_code_all", "drl_score_add",
            # measurement helper (the measured copy-kernel peak)

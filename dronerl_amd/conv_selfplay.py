@@ -1,0 +1,117 @@
+"""`python -m dronerl_amd.conv_selfplay`: shared-policy self-play whose
+learners are conv Q-networks (selfplay.ConvSelfPlayDQN; drl_convselfplay_act).
+
+The command line is `dronerl_amd.selfplay`'s (--learners,
+--drones_per_learner, --drones, --opponents, --grid and `dronerl_amd.train`'s
+options) with --conv_layers / --conv_dense_layers for the learners' shared
+architecture, as `dronerl_amd.conv_league` takes them; --network_type defaults
+to conv here, dense is refused (use `python -m dronerl_amd.selfplay`), and so
+is --use_sharding.
+
+    python -m dronerl_amd.conv_selfplay --learners 1 --drones_per_learner 4 --n_drones 6 \\
+        --grid_size 11 --num_envs 4096 --save_final_checkpoint
+
+After training every learner is saved (checkpoint.save_conv, both formats,
+with --save_final_checkpoint) and the greedy line-up is scored; the JSON line
+is `dronerl_amd.selfplay`'s plus network_type, conv_layers and
+conv_dense_layers.
+"""
+from __future__ import annotations
+
+import json
+import os
+
+from .selfplay import SHARDING_REFUSAL, drones_of, opponents_of
+
+DENSE_REFUSAL = ("conv_selfplay trains conv learners only (--network_type conv); for dense learners use "
+                 "python -m dronerl_amd.selfplay")
+
+
+def parse_args(argv=None):
+    """selfplay.parse_args for conv learners.  Returns (args, points): the
+    shared options (args.learners, args.drones_per_learner, args.drones: the
+    [K][M] map, args.opponents: the drone-index map, args.conv_layers,
+    args.conv_dense_layers) and the grid's points, one per learner or one
+    shared."""
+    import argparse
+
+    from .sweep import expand_grid
+    from .train import parse_args as train_args
+    ap = argparse.ArgumentParser(add_help=False)
+    ap.add_argument("--learners", type=int, default=1)
+    ap.add_argument("--drones_per_learner", type=int, default=2)
+    ap.add_argument("--drones", type=str, default=None)
+    ap.add_argument("--opponents", nargs="*", default=[])
+    ap.add_argument("--grid", type=str, default="{}")
+    ap.add_argument("--network_type", type=str, default="conv")
+    ap.add_argument("--use_sharding", action="store_true", default=False)
+    own, rest = ap.parse_known_args(argv)
+    if own.network_type != "conv":
+        raise ValueError(DENSE_REFUSAL)
+    if own.use_sharding:
+        raise ValueError(SHARDING_REFUSAL)
+    args = train_args(["--network_type", "conv", *rest])
+    drones = drones_of(own.drones, own.learners, own.drones_per_learner, args.n_drones)
+    try:
+        grid = json.loads(own.grid)
+    except json.JSONDecodeError as e:
+        raise ValueError(f"--grid is not valid JSON: {e}")
+    points = expand_grid(grid)
+    if len(points) not in (1, own.learners):
+        raise ValueError(f"--grid has {len(points)} points: one per learner ({own.learners}) or one shared point")
+    args.learners, args.drones_per_learner, args.drones = own.learners, own.drones_per_learner, drones
+    args.opponents = opponents_of(own.opponents, drones, args.n_drones)
+    return args, points
+
+
+def main(argv=None) -> dict:
+    """Train the conv learners on their teams, save every learner, score the
+    greedy line-up."""
+    from datetime import datetime
+
+    import torch
+
+    from .league import learners_of
+    from .selfplay import evaluate_selfplay, train_selfplay
+    from .train import env_params_of
+    args, points = parse_args(argv)
+    hps = learners_of(args, points)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    K, M = args.learners, args.drones_per_learner
+    res = train_selfplay(env_params_of(args), hps, M, args.num_envs, args.num_steps, drones=args.drones,
+                         opponents=args.opponents, reset_env_every=args.reset_env_every,
+                         memory_size=args.memory_size, seed=args.seed, seeds=[args.seed + k for k in range(K)],
+                         device=dev, network_type="conv", conv_layers=args.conv_layers,
+                         conv_dense_layers=tuple(args.conv_dense_layers))
+    out = {"learners": K, "drones_per_learner": M, "drones": args.drones, "num_envs": args.num_envs,
+           "num_steps": args.num_steps, "network_type": "conv", "conv_layers": list(args.conv_layers),
+           "conv_dense_layers": list(args.conv_dense_layers), "steps_per_sec": res.agent_steps_per_s / K,
+           "agent_steps_per_sec": res.agent_steps_per_s, "replay_rows_per_sec": res.rows_per_s,
+           "opponents": {str(d): p for d, p in args.opponents.items()}}
+    if args.save_final_checkpoint:
+        run_dir = os.path.join(args.output_dir, f"conv_selfplay_{datetime.now().strftime('%Y%m%d_%H%M%S')}")
+        os.makedirs(run_dir, exist_ok=True)
+        out["checkpoints"] = []
+        for k in range(K):
+            paths = {}
+            for fmt in ("jax", "torch"):
+                paths[fmt] = os.path.join(run_dir, f"learner_{k}_agent_{args.num_steps}_steps_{fmt}.safetensors")
+                # (the metadata train_jax.py writes: its options as given)
+                res.league.save(k, paths[fmt], format=fmt, conv_layers=args.conv_layers,
+                                hidden_layers=tuple(args.hidden_layers))
+            out["checkpoints"].append(paths)
+    ev = evaluate_selfplay(res, params=env_params_of(args, eval_env=True),
+                           seeds=[args.eval_seed + i for i in range(args.num_evals)], num_steps=args.num_eval_steps,
+                           device=dev, action_seed=args.eval_seed)
+    held = {d: k for k, row in enumerate(args.drones) for d in row}
+    out["eval"] = [{"drone": d, "role": ev["roles"][d], "reward_mean": float(ev["mean"][d]),
+                    "reward_std": float(ev["std"][d]),
+                    **({"final_epsilon": res.league.counters(held[d])["epsilon"],
+                        "train_steps": res.league.counters(held[d])["count"]} if d in held else {})}
+                   for d in range(len(ev["roles"]))]
+    print(json.dumps(out), flush=True)
+    return out
+
+
+if __name__ == "__main__":
+    main()

@@ -1,5 +1,7 @@
-"""Shared-policy self-play: a dense Q-network trained on several drones of
-every env (include/dronerl.h drl_selfplay_*; dronerl_amd/csrc/selfplay/).
+"""Shared-policy self-play: a Q-network trained on several drones of every
+env (include/dronerl.h drl_selfplay_*; dronerl_amd/csrc/selfplay/ for dense
+learners, drl_convselfplay_act and dronerl_amd/csrc/convselfplay/ for conv
+learners).
 
 Reference: torch_impl/helpers/rl_helpers.py:44-65, MultiAgentTrainer.train
 walks its `agents` dict; an agent object that sits under several keys acts
@@ -26,6 +28,9 @@ train_step); the reference's per-key `learn` calls would make M.
     train_selfplay(params, learners, drones_per_learner, num_envs, num_steps) -> SelfPlayResult
     evaluate_selfplay(result)                                    -> the greedy table
     python -m dronerl_amd.selfplay --learners 1 --drones_per_learner 4 --n_drones 6 ...
+
+Conv learners (`ConvSelfPlayDQN`, train_selfplay(network_type="conv")) have
+their own command line, `python -m dronerl_amd.conv_selfplay`.
 """
 from __future__ import annotations
 
@@ -33,12 +38,12 @@ import ctypes
 import json
 import os
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence, Union
 
 import torch
 
 from .dqn import DQNHParams, DrlReplay, DrlWidenetDesc, _check, _on, _stream, _vp
-from .league import U64, LeagueDQN, LeagueLoop, _bind_league, resolve_opponents
+from .league import U64, ConvLeagueDQN, LeagueDQN, LeagueLoop, _bind_convleague, _bind_league, resolve_opponents
 from .params import EnvParams
 from .population import PopulationReplay
 
@@ -58,6 +63,20 @@ def _bind_selfplay(L):
         f.argtypes = args
         f.restype = ctypes.c_int
     L._selfplay_ready = True
+    return L
+
+
+def _bind_convselfplay(L):
+    if getattr(L, "_convselfplay_ready", False):
+        return L
+    from .dqn import DrlConvnetDesc
+    _bind_convleague(L)
+    i32, i64, u64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64
+    D = ctypes.POINTER(DrlConvnetDesc)
+    f = L.drl_convselfplay_act
+    f.argtypes = [D, i32, i32, _vp, _vp, i64, _vp, i32, i32, u64, u64, i64, _vp, i32, _vp, _vp]
+    f.restype = ctypes.c_int
+    L._convselfplay_ready = True
     return L
 
 
@@ -170,6 +189,53 @@ class SelfPlayDQN(LeagueDQN):
         return actions
 
 
+class ConvSelfPlayDQN(ConvLeagueDQN):
+    """SelfPlayDQN for conv learners: K conv learners over the same E envs,
+    learner k on the drones `drones[k]` (K lists of M distinct drone indices;
+    default k * M + j with M = `team`): a ConvPopulationDQN with members = K
+    whose act runs learner k's forward on the code rows of each of its drones
+    and writes those drones' columns of the action matrix
+    (drl_convselfplay_act: the conv league act's tiling on the learner's
+    M * E rows; Q is drl_convpop_act's bit for bit).  `train`, `member_net`,
+    `save`, `params`, `counters` and `sample_slots` are the conv
+    population's."""
+
+    def __init__(self, obs_shape, conv_layers, dense_layers: Sequence[int], hps: Sequence[DQNHParams],
+                 num_envs: int, drones=None, team: int = 1, **kw):
+        super().__init__(obs_shape, conv_layers, dense_layers, hps, num_envs, **kw)
+        _bind_convselfplay(self.L)
+        self.drones = team_map(drones) if drones is not None else default_drones(self.members, int(team))
+        if len(self.drones) != self.members:
+            raise ValueError(f"drones: {len(self.drones)} teams for {self.members} learners")
+        self.team = len(self.drones[0])
+        self._map = _c_map(self.drones)
+
+    def act(self, codes: torch.Tensor, step: int, seed: int = 0, env_offset: int = 0,
+            actions: Optional[torch.Tensor] = None, greedy: bool = False,
+            q: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """SelfPlayDQN.act's arguments, checks and result (q: float32
+        [K, M, E, n_actions])."""
+        K, M, E = self.members, self.team, self.E
+        _on(codes, self.device, torch.uint8, "codes")
+        if codes.dim() != 3 or tuple(codes.shape[1:]) != (E, self.code_bytes) or not codes.is_contiguous():
+            raise ValueError(f"codes must be a contiguous uint8 [n_drones, {E}, {self.code_bytes}] tensor")
+        N = int(codes.shape[0])
+        if actions is None:
+            actions = torch.zeros((E, N), dtype=torch.int32, device=self.device)
+        _on(actions, self.device, torch.int32, "actions")
+        if tuple(actions.shape) != (E, N) or not actions.is_contiguous():
+            raise ValueError(f"actions must be a contiguous int32 [{E}, {N}] tensor")
+        if q is not None:
+            _on(q, self.device, torch.float32, "q")
+            if tuple(q.shape) != (K, M, E, self.n_actions) or not q.is_contiguous():
+                raise ValueError(f"q must be a contiguous float32 [{K}, {M}, {E}, {self.n_actions}] tensor")
+        _check(self.L, self.L.drl_convselfplay_act(
+            ctypes.byref(self.desc), K, self.max_batch, _vp(self.block.data_ptr()), _vp(codes.data_ptr()), E,
+            self._map, M, int(bool(greedy)), int(seed) & U64, int(step), int(env_offset), _vp(actions.data_ptr()), N,
+            None if q is None else _vp(q.data_ptr()), _stream(self.device)))
+        return actions
+
+
 def resolve_team_opponents(opponents, drones, params: EnvParams, device=None) -> Dict[int, object]:
     """league.resolve_opponents for drone indices that no team holds."""
     held = {d: k for k, row in enumerate(drones) for d in row}
@@ -186,7 +252,7 @@ class SelfPlayLoop(LeagueLoop):
     nets' acts, the env step, every drone's next code, the add of every
     team's rows, the train."""
 
-    def __init__(self, env, league: SelfPlayDQN, replay: SelfPlayReplay,
+    def __init__(self, env, league: Union[SelfPlayDQN, ConvSelfPlayDQN], replay: SelfPlayReplay,
                  opponents: Optional[Dict[int, object]] = None, action_seed: int = 2024, act_seed: int = 7):
         super().__init__(env, league, replay, opponents, action_seed=action_seed, act_seed=act_seed)
         held = {d for row in league.drones for d in row}
@@ -201,7 +267,7 @@ class SelfPlayLoop(LeagueLoop):
 @dataclass
 class SelfPlayResult:
     env: object
-    league: SelfPlayDQN
+    league: Union[SelfPlayDQN, ConvSelfPlayDQN]
     replay: SelfPlayReplay
     steps: int
     agent_steps_per_s: float   # learner steps (one per learner and env step) per second
@@ -213,7 +279,8 @@ def train_selfplay(params: EnvParams, learners: Sequence[DQNHParams], drones_per
                    num_steps: int, hidden: Sequence[int] = (128, 64), drones=None, opponents=None,
                    reset_env_every: int = 100, memory_size: int = 100_000, seed: int = 0, env_offset: int = 0,
                    action_seed: int = 2024, act_seed: int = 7, seeds: Optional[Sequence[int]] = None, on_step=None,
-                   device=None) -> SelfPlayResult:
+                   device=None, network_type: str = "dense", conv_layers=None,
+                   conv_dense_layers: Sequence[int] = ()) -> SelfPlayResult:
     """train_league with every learner on `drones_per_learner` drones: per
     step the synthetic columns, the self-play act (the teams' columns), the
     fixed opponents' greedy acts, one env step, every drone's next code, the
@@ -223,10 +290,16 @@ def train_selfplay(params: EnvParams, learners: Sequence[DQNHParams], drones_per
     k * M + j); opponents: {drone index in no team: net | checkpoint path |
     None}, missing indices are random; seeds: each learner's initialisation
     seed (default `seed` for all).  on_step(t, league, replay, actions,
-    rewards, dones): called between step t's add and its train (tests)."""
+    rewards, dones): called between step t's add and its train (tests).
+    network_type "conv": every learner a conv net (a ConvSelfPlayDQN of
+    conv_layers, default train_jax.py's one 3x3 layer of 8 channels, padding
+    1, and conv_dense_layers; `hidden` is then unused), as train_league takes
+    them."""
     from .env import BatchedDeliveryDrones
     if num_steps < 1 or reset_env_every < 1:
         raise ValueError("num_steps and reset_env_every must be >= 1")
+    if network_type not in ("dense", "conv"):
+        raise ValueError("network_type must be 'dense' or 'conv'")
     learners = list(learners)
     K, M, E, N = len(learners), int(drones_per_learner), int(num_envs), params.n_drones
     if K < 1 or M < 1 or K * M > N:
@@ -240,7 +313,13 @@ def train_selfplay(params: EnvParams, learners: Sequence[DQNHParams], drones_per
     dev = env.device
     opp = resolve_team_opponents(opponents, drones, params, dev)
     seeds = seeds if seeds is not None else [seed] * K
-    league = SelfPlayDQN((2 * r + 1) ** 2 * 6, hidden, learners, E, drones=drones, device=dev, seeds=seeds)
+    if network_type == "conv":
+        from .checkpoint import TRAIN_JAX_CONV_LAYERS
+        W = 2 * r + 1
+        league = ConvSelfPlayDQN((W, W, 6), conv_layers if conv_layers is not None else TRAIN_JAX_CONV_LAYERS,
+                                 tuple(conv_dense_layers), learners, E, drones=drones, device=dev, seeds=seeds)
+    else:
+        league = SelfPlayDQN((2 * r + 1) ** 2 * 6, hidden, learners, E, drones=drones, device=dev, seeds=seeds)
     rb = SelfPlayReplay(K, memory_size, r, device=dev)
     loop = SelfPlayLoop(env, league, rb, opp, action_seed=action_seed, act_seed=act_seed)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -292,8 +371,9 @@ def evaluate_selfplay(result_or_nets, params: Optional[EnvParams] = None, drones
 
 
 # ------------------------------------------------------------ command line --
-CONV_LEARNERS_REFUSAL = ("--network_type conv: self-play learners are dense nets (conv learners train one drone each "
-                         "with python -m dronerl_amd.conv_league; conv checkpoints work as --opponents)")
+CONV_LEARNERS_REFUSAL = ("--network_type conv: this command's self-play learners are dense nets (conv learners train one "
+                         "drone each with python -m dronerl_amd.conv_league and several with python -m "
+                         "dronerl_amd.conv_selfplay; conv checkpoints work as --opponents)")
 SHARDING_REFUSAL = ("self-play runs on one GPU (no --use_sharding): python -m dronerl_amd.train --use_sharding shards "
                     "one learner on drone 0")
 

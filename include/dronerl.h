@@ -1127,6 +1127,26 @@ int drl_selfplay_replay_add(const drl_widenet_desc* d, int32_t members, const dr
                             int64_t num_envs, const int32_t* drones, int32_t team, const void* d_codes_prev,
                             const void* d_codes, const int32_t* d_actions, const float* d_rewards,
                             const uint8_t* d_dones, int32_t n_drones, hipStream_t stream);
+/* drl_selfplay_act's arguments, rule and streams for learners that are
+ * members of a drl_convpop_layout block (initialised by drl_convpop_init,
+ * trained by drl_convpop_train, sampled by drl_convpop_sample_rows; the rings
+ * are fed by drl_selfplay_replay_add, which reads the code window and the
+ * member count of its description alone).  For learner k, team slot j and env
+ * i, with dr = drones[k][j]: the action of the learner's online set on
+ * d_codes[dr][i] into d_actions[i * n_drones + dr] and NO column outside the
+ * teams, its draw explore_draw(seed + dr, step, env_offset + i, n_actions,
+ * epsilon_k), or none with greedy != 0.  The forward is the conv learner's
+ * own per-row forward (drl_convpop_act's: taps in (ci, ky, kx) order, a dense
+ * unit's 64 partial sums and xor tree, nothing contracted); d_q is nullable,
+ * [members][team][E][n_actions].  The tiling is drl_convleague_act_plan_query's
+ * with a tile of env_tile consecutive rows r = j * E + i of one learner
+ * (team * num_envs < 2^31).  With team = 1 and drones[k][0] = k the actions
+ * and d_q are drl_convleague_act's byte for byte.  Graph-capturable, as both
+ * of those calls. */
+int drl_convselfplay_act(const drl_convnet_desc* d, int32_t members, int32_t max_batch, const void* d_pop,
+                         const void* d_codes, int64_t num_envs, const int32_t* drones /* HOST [members][team] */,
+                         int32_t team, int32_t greedy, uint64_t seed, uint64_t step, int64_t env_offset,
+                         int32_t* d_actions, int32_t n_drones, float* d_q, hipStream_t stream);
 
 #ifdef __cplusplus
 }
