@@ -9,7 +9,9 @@ Dense kernel is the transpose) and packs them for the MFMA kernel
 (drl_qnet_pack) whenever they change; `act` runs the forward + epsilon-greedy
 choice for every env in one launch (drl_qnet_act; f32 numerics by default,
 bf16 operands as an opt-in).  `ReplayBuffer.add_many` is drl_replay_add; `sample` is plain
-torch indexing (64 rows).
+torch indexing (64 rows).  `PrioritizedReplay` / `PrioritizedDQNLearner`: proportional
+prioritized replay on the device (drl_per_*, drl_dqn_per_train), an option
+the reference does not have.
 """
 from __future__ import annotations
 
@@ -64,6 +66,18 @@ class DrlDqnLayout(ctypes.Structure):
                 ("bytes", ctypes.c_int64), ("grad_workgroups", ctypes.c_int32), ("grad_lds_bytes", ctypes.c_int32)]
 
 
+class DrlPerHParams(ctypes.Structure):
+    _fields_ = [("alpha", ctypes.c_double), ("beta0", ctypes.c_double), ("beta_steps", ctypes.c_int64),
+                ("eps", ctypes.c_double)]
+
+
+class DrlPerLayout(ctypes.Structure):
+    _fields_ = [("capacity", ctypes.c_int64), ("leaves", ctypes.c_int64), ("batch", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("tree_off", ctypes.c_int64), ("pmax_off", ctypes.c_int64),
+                ("wmax_off", ctypes.c_int64), ("slots_off", ctypes.c_int64), ("weights_off", ctypes.c_int64),
+                ("absd_off", ctypes.c_int64), ("bytes", ctypes.c_int64)]
+
+
 _vp = ctypes.c_void_p
 
 
@@ -94,6 +108,13 @@ def _bind(L):
         "drl_dqn_large_init": [D, i32, _vp, f32, _vp],
         "drl_dqn_large_train": [D, ctypes.POINTER(DrlDqnHParams), _vp, _vp, ctypes.POINTER(DrlReplay), i64, _vp],
         "drl_dqn_large_sample_rows": [D, ctypes.POINTER(DrlDqnHParams), _vp, i64, _vp, _vp],
+        "drl_per_layout_query": [i64, i32, ctypes.POINTER(DrlPerLayout)],
+        "drl_per_init": [i64, i32, _vp, _vp],
+        "drl_per_mark_new": [i64, i32, _vp, i64, i64, _vp],
+        "drl_per_rebuild": [i64, i32, _vp, _vp],
+        "drl_per_sample": [i64, i32, _vp, ctypes.POINTER(DrlPerHParams), u64, _vp, i64, _vp],
+        "drl_dqn_per_train": [D, ctypes.POINTER(DrlDqnHParams), ctypes.POINTER(DrlPerHParams), _vp, _vp,
+                              ctypes.POINTER(DrlReplay), i64, _vp, _vp],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -1151,13 +1172,179 @@ class WideDQNLearner(LargeBatchDQNLearner):
     _bound = staticmethod(lambda L: _bind_widenet(_bind(L)))
 
 
-def make_learner(net, hp: Optional[DQNHParams] = None, **kw):
+PER_MAX_CAPACITY = 1 << 24  # DRL_PER_MAX_CAPACITY
+PER_NET_REFUSAL = ("prioritized replay trains dense nets of hidden widths up to 128 (a QNetwork) only: conv and "
+                   "wide nets are not implemented")
+
+
+class PrioritizedReplay:
+    """Proportional prioritized replay (Schaul et al. 2016) around a
+    ReplayBuffer, which stays as it is: a priority sum tree over the ring's
+    slots on the device (drl_per_*; include/dronerl.h describes the block).
+    `add_many` and the fused env step (`env.step(..., replay=per)`) are the
+    ring's own, followed by drl_per_mark_new: the new rows enter with the
+    largest priority assigned so far (rows added through the wrapped ring
+    directly are not marked and are never drawn).
+    PrioritizedDQNLearner.train(per) draws by priority and writes the new
+    priorities back.
+
+    alpha: priority = (|td error| + eps) ** alpha (0: uniform over the
+    written slots); beta0, beta_steps: the importance exponent, annealed
+    linearly from beta0 to 1 over beta_steps learner steps (0: beta0
+    throughout).  `batch` is fixed by the first learner that trains on it (or
+    here).  Views of the block: `tree` (f32 [2P]), `pmax`, `wmax` (f32 [1]),
+    `slots` (int64 [batch]) and `weights` (f32 [batch]) of the last step."""
+
+    def __init__(self, rb: ReplayBuffer, alpha: float = 0.6, beta0: float = 0.4, beta_steps: int = 0,
+                 eps: float = 1e-6, batch: Optional[int] = None):
+        if not isinstance(rb, ReplayBuffer):
+            raise ValueError("PrioritizedReplay wraps a dqn.ReplayBuffer (sharded replay is not implemented)")
+        if not alpha >= 0:
+            raise ValueError("alpha must be >= 0")
+        if not 0 <= beta0 <= 1:
+            raise ValueError("beta0 must be in [0, 1]")
+        if beta_steps < 0:
+            raise ValueError("beta_steps must be >= 0")
+        if not eps >= 0:
+            raise ValueError("eps must be >= 0")
+        self.rb, self.L = rb, _bind(rb.L)
+        self.alpha, self.beta0, self.beta_steps, self.eps = float(alpha), float(beta0), int(beta_steps), float(eps)
+        self._hp = DrlPerHParams(self.alpha, self.beta0, self.beta_steps, self.eps)
+        self.batch = None
+        # (cursor, count) of the rows written before the block exists: the ring's contents as wrapped, then the adds
+        self._pending = [(0 if rb.size < rb.capacity else rb.cursor, rb.size)] if rb.size else []
+        if batch is not None:
+            self.bind(batch)
+
+    capacity = property(lambda self: self.rb.capacity)
+    size = property(lambda self: self.rb.size)
+    cursor = property(lambda self: self.rb.cursor)
+
+    def bind(self, batch: int):
+        """Allocate the block for learner steps of `batch` rows (once)."""
+        if self.batch is not None:
+            if int(batch) != self.batch:
+                raise ValueError(f"this PrioritizedReplay is laid out for batch {self.batch}, not {batch}")
+            return self
+        lay = DrlPerLayout()
+        if self.L.drl_per_layout_query(self.rb.capacity, int(batch), ctypes.byref(lay)):
+            raise ValueError(self.L.drl_last_error().decode())
+        self.layout, self.batch = lay, int(batch)
+        dev = self.rb.obs.device
+        self.block = torch.zeros(lay.bytes, dtype=torch.uint8, device=dev)
+
+        def view(off, n, dt, size):
+            return self.block[off:off + n * size].view(dt)
+
+        self.tree = view(lay.tree_off, 2 * lay.leaves, torch.float32, 4)
+        self.pmax = view(lay.pmax_off, 1, torch.float32, 4)
+        self.wmax = view(lay.wmax_off, 1, torch.float32, 4)
+        self.slots = view(lay.slots_off, self.batch, torch.int64, 8)
+        self.weights = view(lay.weights_off, self.batch, torch.float32, 4)
+        self.abs_td = view(lay.absd_off, self.batch, torch.float32, 4)
+        _check(self.L, self.L.drl_per_init(self.rb.capacity, self.batch, _vp(self.block.data_ptr()), _stream(dev)))
+        for cursor, count in self._pending:
+            self._mark(cursor, count)
+        self._pending = []
+        return self
+
+    def _mark(self, cursor: int, count: int):
+        if self.batch is None:
+            self._pending.append((cursor, count))
+            if sum(n for _, n in self._pending) >= self.rb.capacity:
+                self._pending = [(0, self.rb.capacity)]
+            return
+        _check(self.L, self.L.drl_per_mark_new(self.rb.capacity, self.batch, _vp(self.block.data_ptr()), int(cursor),
+                                               int(count), _stream(self.rb.obs.device)))
+
+    def add_many(self, obs, actions, rewards, next_obs, dones):
+        """ReplayBuffer.add_many, then the new rows' leaves = pmax."""
+        cursor = self.rb.cursor
+        batch = self.rb.add_many(obs, actions, rewards, next_obs, dones)
+        self._mark(cursor, obs.shape[0])
+        return batch
+
+    def _add_from_step(self, env, *a, **kw):
+        cursor = self.rb.cursor
+        batch = self.rb._add_from_step(env, *a, **kw)
+        self.last_batch = batch
+        self._mark(cursor, env.num_envs)
+        return batch
+
+    def rebuild(self):
+        """Every internal node from the leaves (drl_per_rebuild)."""
+        _check(self.L, self.L.drl_per_rebuild(self.rb.capacity, self.batch, _vp(self.block.data_ptr()),
+                                              _stream(self.rb.obs.device)))
+
+    def sample(self, seed: int, d_counters: int, size: Optional[int] = None):
+        """drl_per_sample at the step the device counters at `d_counters`
+        hold, from the tree as it stands (rebuild() first): fills `slots`,
+        `weights` and `wmax`."""
+        _check(self.L, self.L.drl_per_sample(self.rb.capacity, self.batch, _vp(self.block.data_ptr()),
+                                             ctypes.byref(self._hp), int(seed) & (2**64 - 1), _vp(d_counters),
+                                             self.rb.size if size is None else int(size),
+                                             _stream(self.rb.obs.device)))
+
+
+class PrioritizedDQNLearner(LargeBatchDQNLearner):
+    """LargeBatchDQNLearner on prioritized rows (drl_dqn_per_train): the
+    same agent block, launch chain and arithmetic, at every batch 1..4096.
+    `train(per)` takes a PrioritizedReplay: rebuild, stratified draw, the
+    chain with each row's importance weight on its squared error and on the
+    Q head's delta, the new priorities (|td error| + eps) ** alpha written
+    to the drawn slots -- stream-ordered, no synchronisation,
+    graph-capturable.  With alpha = 0 and beta = 0 every weight and priority
+    is exactly 1.0 and the step is oracle/dqn_learner.py's on the drawn
+    rows."""
+
+    def __init__(self, net: QNetwork, hp: Optional[DQNHParams] = None, target=None,
+                 generator: Optional[torch.Generator] = None):
+        if not isinstance(net, QNetwork):
+            raise ValueError(PER_NET_REFUSAL)
+        super().__init__(net, hp, target=target, generator=generator)
+
+    def train(self, per: "PrioritizedReplay"):
+        """One learner block on the prioritized replay's current contents."""
+        if not isinstance(per, PrioritizedReplay):
+            raise ValueError("PrioritizedDQNLearner.train takes a PrioritizedReplay")
+        if per.rb.obs.device != self.block.device:
+            raise ValueError("the replay buffer must be on the learner's device")
+        per.bind(self.hp.batch)
+        _check(self.L, self.L.drl_dqn_per_train(ctypes.byref(self.net.desc), ctypes.byref(self._hp),
+                                                ctypes.byref(per._hp), _vp(self.block.data_ptr()),
+                                                _vp(self.net.packed.data_ptr()), ctypes.byref(per.rb._c), per.rb.size,
+                                                _vp(per.block.data_ptr()), _stream(self.block.device)))
+
+    def sample_slots(self, per: "PrioritizedReplay", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The replay slots (int64 [batch]) the next train(per) draws: a
+        rebuild and a draw at the device step (their weights are left in
+        per.weights); stream-ordered, no sync.  `out`: a copy's destination
+        (default: a new tensor)."""
+        if not isinstance(per, PrioritizedReplay):
+            raise ValueError("PrioritizedDQNLearner.sample_slots takes a PrioritizedReplay")
+        per.bind(self.hp.batch)
+        per.rebuild()
+        per.sample(self.hp.sample_seed, self.block.data_ptr() + self.layout.counters_off)
+        if out is None:
+            return per.slots.clone()
+        _on(out, self.block.device, torch.int64, "out")
+        if out.numel() != self.hp.batch or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous int64 [{self.hp.batch}] tensor")
+        return out.copy_(per.slots)
+
+
+def make_learner(net, hp: Optional[DQNHParams] = None, per: bool = False, **kw):
     """A net's learner: for a QNetwork by hp.batch, DQNLearner (one launch,
     batches up to 64) or LargeBatchDQNLearner (a launch chain, batches up to
     4096); for a WideQNetwork, WideDQNLearner (the launch chain at every
     batch); for a ConvQNetwork by hp.batch, ConvDQNLearner (batches up to 64)
-    or LargeBatchConvDQNLearner (chunked gradients, batches up to 4096)."""
+    or LargeBatchConvDQNLearner (chunked gradients, batches up to 4096).
+    per=True: PrioritizedDQNLearner at every batch (a QNetwork only)."""
     hp = hp or DQNHParams()
+    if per:
+        if isinstance(net, (WideQNetwork, ConvQNetwork)):
+            raise ValueError(PER_NET_REFUSAL)
+        return PrioritizedDQNLearner(net, hp, **kw)
     if isinstance(net, WideQNetwork):
         return WideDQNLearner(net, hp, **kw)
     if isinstance(net, ConvQNetwork):

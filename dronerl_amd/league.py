@@ -487,6 +487,8 @@ def parse_args(argv=None):
     ap.add_argument("--grid", type=str, default="{}")
     own, rest = ap.parse_known_args(argv)
     args = train_args(rest)
+    from .train import refuse_prioritized
+    refuse_prioritized(args, "the league")
     if args.network_type != "dense":
         raise ValueError(CONV_LEARNERS_REFUSAL)
     if args.use_sharding:

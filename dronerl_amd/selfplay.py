@@ -448,6 +448,8 @@ def parse_args(argv=None):
     ap.add_argument("--grid", type=str, default="{}")
     own, rest = ap.parse_known_args(argv)
     args = train_args(rest)
+    from .train import refuse_prioritized
+    refuse_prioritized(args, "self-play")
     if args.network_type != "dense":
         raise ValueError(CONV_LEARNERS_REFUSAL)
     if args.use_sharding:

@@ -70,6 +70,8 @@ def parse_args(argv=None):
     ap.add_argument("--members_seeds", type=int, default=1)
     own, rest = ap.parse_known_args(argv)
     args = train_args(rest)
+    from .train import refuse_prioritized
+    refuse_prioritized(args, "the population sweep")
     try:
         grid = json.loads(own.grid)
     except json.JSONDecodeError as e:

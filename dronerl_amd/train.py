@@ -8,7 +8,8 @@ the drone-0 transitions in the replay ring (drl_step_code_replay:
 buffer.add_many), the learner block (drl_dqn_train: sample + train_step when
 the buffer can sample, the target update, the epsilon decay, step + 1; a
 conv net: drl_convnet_act and drl_convnet_dqn_train; a dense net wider than
-128: drl_widenet_act and drl_widenet_dqn_train), and
+128: drl_widenet_act and drl_widenet_dqn_train; --prioritized_replay: the
+ring wrapped in dqn.PrioritizedReplay and drl_dqn_per_train), and
 a reset of every env when step % reset_env_every == 0 (:99-113).
 `evaluate` is eval_jax (:270-319): greedy drone 0 against random drones,
 episodes sharded over ranks with the eval table all-reduced
@@ -41,8 +42,8 @@ class TrainResult:
 def train(params: EnvParams, num_envs: int, num_steps: int, hidden: Sequence[int] = (128, 64), hp=None,
           reset_env_every: int = 100, memory_size: int = 100_000, seed: int = 0, env_offset: int = 0,
           action_seed: int = 2024, act_seed: int = 7, device=None, rank: int = 0, world: int = 1,
-          group=None, network_type: str = "dense", conv_layers=None, conv_dense_layers: Sequence[int] = ()
-          ) -> TrainResult:
+          group=None, network_type: str = "dense", conv_layers=None, conv_dense_layers: Sequence[int] = (),
+          per: Optional[dict] = None) -> TrainResult:
     """train_jax.py's training loop (see the module docstring).  hp: a
     dqn.DQNHParams (default: train_jax.py's defaults with num_steps, so
     epsilon decays as :133-134 schedules it).  hidden: 1-3 widths, each a
@@ -66,8 +67,14 @@ def train(params: EnvParams, num_envs: int, num_steps: int, hidden: Sequence[int
     rank * num_envs / world .. (num_envs % world == 0, :401-402), the one
     replay ring is sharded (global_learner.ShardedReplay) and every rank runs
     the same learner; env_offset is then ignored.  The returned rate counts
-    every rank's envs."""
-    from .dqn import ConvQNetwork, DQNHParams, QNetwork, ReplayBuffer, WideQNetwork, is_wide, make_learner
+    every rank's envs.
+
+    per (--prioritized_replay): dqn.PrioritizedReplay's keywords (alpha,
+    beta0, beta_steps, eps).  The ring is wrapped in a PrioritizedReplay and
+    the learner is dqn.PrioritizedDQNLearner at every batch; dense nets of
+    widths up to 128 on one GPU only.  The returned `replay` is the wrapper."""
+    from .dqn import (ConvQNetwork, DQNHParams, PrioritizedReplay, QNetwork, ReplayBuffer, WideQNetwork, is_wide,
+                      make_learner)
     from .distributed import shard_envs
     from .env import BatchedDeliveryDrones
     from .global_learner import ShardedReplay
@@ -80,6 +87,13 @@ def train(params: EnvParams, num_envs: int, num_steps: int, hidden: Sequence[int
     wide = network_type == "dense" and is_wide(hidden)
     if wide and world > 1:
         raise ValueError(WIDE_SHARDING_REFUSAL)
+    if per is not None:
+        if network_type == "conv":
+            raise ValueError(PER_CONV_REFUSAL)
+        if wide:
+            raise ValueError(PER_WIDE_REFUSAL)
+        if world > 1:
+            raise ValueError(PER_SHARDING_REFUSAL)
     shard = shard_envs(num_envs, rank, world) if world > 1 else None
     env = BatchedDeliveryDrones(params, shard.num_envs if shard else num_envs, device=device,
                                 env_offset=shard.env_offset if shard else env_offset)
@@ -101,14 +115,18 @@ def train(params: EnvParams, num_envs: int, num_steps: int, hidden: Sequence[int
         learner = make_learner(net, hp, generator=torch.Generator().manual_seed(seed + 1))
     else:
         net = QNetwork(D, tuple(hidden), device=dev, generator=torch.Generator().manual_seed(seed), input="code")
-        # (batches up to 64: DQNLearner's one launch; up to 4096: LargeBatchDQNLearner's launch chain)
-        learner = make_learner(net, hp, generator=torch.Generator().manual_seed(seed + 1))
+        # (batches up to 64: DQNLearner's one launch; up to 4096: LargeBatchDQNLearner's launch chain; prioritized
+        # replay: PrioritizedDQNLearner's chain at every batch)
+        learner = make_learner(net, hp, generator=torch.Generator().manual_seed(seed + 1),
+                               **({"per": True} if per is not None else {}))
     if shard:
         rb = ShardedReplay(memory_size, D, dev, num_envs, shard.env_offset, shard.num_envs, rank, world,
                            code_radius=r, group=group)
         ring = rb.ring
     else:
         rb = ring = ReplayBuffer(memory_size, D, dev, code_radius=r)
+        if per is not None:  # (the ring with its priority tree: the step's add marks the new rows)
+            rb = ring = PrioritizedReplay(rb, batch=hp.batch, **per)
     code = [env.new_code(), env.new_code()]
     env.get_code(out=code[0])
     acts = torch.empty((E, N), dtype=torch.int32, device=dev)
@@ -150,6 +168,12 @@ def train(params: EnvParams, num_envs: int, num_steps: int, hidden: Sequence[int
 
 CONV_SHARDING_REFUSAL = ("--use_sharding with --network_type conv is not implemented: the global (sharded) "
                          "learner trains dense nets only")
+PER_CONV_REFUSAL = ("--prioritized_replay with --network_type conv is not implemented: prioritized replay trains "
+                    "dense nets only")
+PER_WIDE_REFUSAL = ("--prioritized_replay with --hidden_layers wider than 128 is not implemented: prioritized replay "
+                    "trains dense nets of widths up to 128 only")
+PER_SHARDING_REFUSAL = ("--prioritized_replay with --use_sharding is not implemented: the priority tree covers one "
+                        "GPU's ring")
 WIDE_SHARDING_REFUSAL = ("--use_sharding with --hidden_layers wider than 128 is not implemented: the global "
                          "(sharded) learner trains dense nets of widths up to 128 only")
 
@@ -229,6 +253,13 @@ def parse_args(argv=None):
     ap.add_argument("--num_eval_steps", type=int, default=10_000)
     ap.add_argument("--num_evals", type=int, default=5)
     ap.add_argument("--output_dir", default="output")
+    ap.add_argument("--prioritized_replay", action="store_true", default=False,
+                    help="draw the replay rows by priority (proportional prioritized replay on the device)")
+    ap.add_argument("--per_alpha", type=float, default=0.6, help="priority = (|td error| + per_eps) ** per_alpha")
+    ap.add_argument("--per_beta", type=float, default=0.4, help="the importance exponent at step 0")
+    ap.add_argument("--per_beta_steps", type=int, default=None,
+                    help="learner steps over which beta anneals to 1 (default: num_steps; 0: per_beta throughout)")
+    ap.add_argument("--per_eps", type=float, default=1e-6)
     args = ap.parse_args(argv)
     # train_jax.py:393-402's validations
     if args.num_envs <= 0:
@@ -241,7 +272,32 @@ def parse_args(argv=None):
         raise ValueError(CONV_SHARDING_REFUSAL)
     if args.use_sharding and args.network_type == "dense" and max(args.hidden_layers) > 128:
         raise ValueError(WIDE_SHARDING_REFUSAL)
+    if args.per_beta_steps is None:
+        args.per_beta_steps = args.num_steps  # (the usual anneal to 1 over the run)
+    if args.prioritized_replay:
+        if args.network_type == "conv":
+            raise ValueError(PER_CONV_REFUSAL)
+        if max(args.hidden_layers) > 128:
+            raise ValueError(PER_WIDE_REFUSAL)
+        if args.use_sharding:
+            raise ValueError(PER_SHARDING_REFUSAL)
+        if args.per_alpha < 0 or not 0 <= args.per_beta <= 1 or args.per_beta_steps < 0 or args.per_eps < 0:
+            raise ValueError("--per_alpha and --per_eps must be >= 0, --per_beta in [0, 1], --per_beta_steps >= 0")
     return args
+
+
+def per_options_of(args) -> Optional[dict]:
+    """PrioritizedReplay's keywords from the command line (None: uniform replay)."""
+    if not args.prioritized_replay:
+        return None
+    return dict(alpha=args.per_alpha, beta0=args.per_beta, beta_steps=args.per_beta_steps, eps=args.per_eps)
+
+
+def refuse_prioritized(args, driver: str):
+    """The drivers that train several learners draw uniformly: --prioritized_replay is refused by name."""
+    if getattr(args, "prioritized_replay", False):
+        raise ValueError(f"--prioritized_replay is not implemented for {driver}: it trains one dense agent "
+                         "(python -m dronerl_amd.train)")
 
 
 def _parse_conv_layers(value: str):
@@ -302,7 +358,8 @@ def main(argv=None) -> dict:
     res = train(env_params_of(args), args.num_envs, args.num_steps, hidden=tuple(args.hidden_layers),
                 hp=hparams_of(args), reset_env_every=args.reset_env_every, memory_size=args.memory_size,
                 seed=args.seed, device=dev, rank=rank, world=world, network_type=args.network_type,
-                conv_layers=args.conv_layers, conv_dense_layers=tuple(args.conv_dense_layers))
+                conv_layers=args.conv_layers, conv_dense_layers=tuple(args.conv_dense_layers),
+                per=per_options_of(args))
     metrics = {"obs_per_sec": res.env_steps_per_s, "time_taken": args.num_envs * args.num_steps / res.env_steps_per_s,
                "num_gpus": world}
     run_dir = os.path.join(args.output_dir, f"jax_run_{datetime.now().strftime('%Y%m%d_%H%M%S')}")

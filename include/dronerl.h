@@ -645,6 +645,70 @@ int drl_dqn_large_sample_rows(const drl_qnet_desc* d, const drl_dqn_hparams* h, 
                               int64_t* d_slots, hipStream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Prioritized experience replay (Schaul et al. 2016, proportional variant)
+ * for drl_dqn_large_train's learner: the reference samples uniformly
+ * (jax_impl/buffers.py:79-90); this is an option beside it.  A priority sum
+ * tree over the ring's slots lives in one caller-owned device block
+ * (drl_per_layout, 16-B aligned):
+ *   P = the smallest power of two >= capacity; float tree[2P] in heap order:
+ *   tree[1] the root, node i's children 2i and 2i + 1, slot s's leaf
+ *   tree[P + s], tree[0] unused.  A leaf holds the slot's priority already
+ *   raised to alpha (0.0: never written, or a pad leaf s >= capacity); every
+ *   internal node is tree[2i] + tree[2i + 1] as one f32 addition.
+ * pmax (f32, 1.0 after drl_per_init) is the largest priority ever assigned;
+ * new transitions enter with it (drl_per_mark_new after any add).  The block
+ * also holds one step's drawn slots (int64 [batch]), their importance weights
+ * (f32 [batch], already divided by wmax), wmax, and the rows' |TD error|.
+ * Every call validates its arguments before any device work, is
+ * stream-ordered, allocates nothing and does not synchronise.
+ * ------------------------------------------------------------------------ */
+#define DRL_PER_MAX_CAPACITY (1 << 24)
+typedef struct drl_per_hparams {
+    double alpha;        /* >= 0: priority = (|td error| + eps)^alpha; 0 = uniform over the written slots */
+    double beta0;        /* in [0, 1]: the importance exponent at step 0 */
+    int64_t beta_steps;  /* >= 0: beta = beta0 + (1 - beta0) * min(1, step / beta_steps); 0: beta0 throughout */
+    double eps;          /* >= 0 */
+} drl_per_hparams;
+typedef struct drl_per_layout {
+    int64_t capacity, leaves;  /* leaves = P */
+    int32_t batch, reserved;
+    int64_t tree_off, pmax_off, wmax_off, slots_off, weights_off, absd_off, bytes;  /* bytes, multiples of 16 */
+} drl_per_layout;
+/* Host only.  capacity in [1, DRL_PER_MAX_CAPACITY], batch in [1, DRL_DQN_LARGE_MAX_BATCH]. */
+int drl_per_layout_query(int64_t capacity, int32_t batch, drl_per_layout* layout);
+/* The tree zeroed, pmax = 1. */
+int drl_per_init(int64_t capacity, int32_t batch, void* d_per, hipStream_t stream);
+/* The leaves of slots [cursor, cursor + count) mod capacity = pmax (drl_replay_add's slots for the same cursor
+ * and n; count > capacity marks every slot).  The internal nodes are refreshed by the next rebuild. */
+int drl_per_mark_new(int64_t capacity, int32_t batch, void* d_per, int64_t cursor, int64_t count, hipStream_t stream);
+/* Every internal node from the leaves (two launches at most). */
+int drl_per_rebuild(int64_t capacity, int32_t batch, void* d_per, hipStream_t stream);
+/* The block's slots, weights and wmax for the step the counters at d_counters (a drl_dqn_counters on the device:
+ * an agent block's counters_off) hold, from a rebuilt tree with a positive root -- stratified, one row per
+ * stratum; all f32 unless stated:
+ *   h = splitmix64(seed ^ splitmix64(((uint64)(uint32)step << 16) | b))      (drl_dqn_sample_rows' hash)
+ *   u = (float)(h >> 40) * 2^-24;  m = ((float)b + u) / (float)batch * tree[1]
+ *   i = 1; while i < P: l = tree[2i], r = tree[2i + 1];
+ *                       if r == 0 or m < l: i = 2i; else: m = m - l, i = 2i + 1
+ *   slot = i - P     (the walk never enters a node of value 0.0, so the slot has been written)
+ *   w = (float)pow((double)size * ((double)tree[P + slot] / (double)tree[1]), -beta)   (beta: double)
+ *   wmax = max_b w;  weights[b] = w / wmax
+ * size in [1, capacity]: the ring's current size. */
+int drl_per_sample(int64_t capacity, int32_t batch, void* d_per, const drl_per_hparams* ph, uint64_t seed,
+                   const void* d_counters, int64_t size, hipStream_t stream);
+/* drl_dqn_large_train on prioritized rows (its arguments, agent block, launch chain and arithmetic; dense nets
+ * of drl_qnet_desc, f32 or policy-code rows, batch 1..4096; d_per laid out for (r->capacity, h->batch)):
+ * rebuild, sample (seed h->sample_seed, the agent's counters), the rows at the drawn slots, each layer's forward
+ * of both nets, the TD error d = q - td with the row's squared error w * (d * d) and the Q head's delta
+ * w * ((d + d) / batch), the priority update, each layer's backward, the update, the counters, the re-pack.
+ * The priority update: p = (float)pow((double)|d| + eps, alpha), at most 2^64 (a NaN becomes 2^64), stored in the
+ * slot's leaf; a slot drawn by several rows takes the largest of their values; pmax = max(pmax, p).  With
+ * size < h->batch it is drl_dqn_large_train's no-sample step and the tree is left alone.  alpha = 0 and
+ * beta0 = 0, beta_steps = 0 give weights and priorities of exactly 1.0.  Graph-capturable. */
+int drl_dqn_per_train(const drl_qnet_desc* d, const drl_dqn_hparams* h, const drl_per_hparams* ph, void* d_agent,
+                      void* d_packed, const struct drl_replay* r, int64_t size, void* d_per, hipStream_t stream);
+
+/* ------------------------------------------------------------------------
  * Convolutional Q-networks (torch_impl/agents/dqn.py:85-159 ConvQNetwork,
  * jax_impl/agents/dqn.py:66-94; sample_models/dqn-agent-5 is one): inference
  * (drl_convnet_pack, drl_convnet_act) and, below, the learner
