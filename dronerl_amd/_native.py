@@ -62,6 +62,10 @@ EXPORTS = ["drl_abi_version", "drl_last_error", "drl_side_from_density", "drl_la
            # a population of dense DQN agents in one launch chain (dronerl_amd.population)
            "drl_pop_layout_query", "drl_pop_init", "drl_pop_act", "drl_pop_replay_add", "drl_pop_train",
            "drl_pop_sample_rows",
+           # ... with prioritized replay, a tree and PER hyperparameters per member
+           # (dronerl_amd.population.PrioritizedPopulationDQN)
+           "drl_pop_per_layout_query", "drl_pop_per_init", "drl_pop_per_mark_new", "drl_pop_per_rebuild",
+           "drl_pop_per_sample", "drl_pop_per_train",
            # a population of conv DQN agents in one launch chain (dronerl_amd.population.ConvPopulationDQN)
            "drl_convpop_layout_query", "drl_convpop_init", "drl_convpop_act", "drl_convpop_train",
            "drl_convpop_sample_rows",

@@ -17,6 +17,8 @@
 //                            leaf zeroed; the priority kernel then raises each drawn leaf to its rows' largest new
 //                            priority with an integer max on the float's bits (positive floats order as unsigned
 //                            integers), and pmax the same way.
+// The rebuild's, the sampler's, the rows', the TD's and the priority kernel's bodies live in dronerl_per_chain.h,
+// which the prioritized population (perpop/dronerl_perpop.hip) includes too.
 // No workgroup waits for another and no float atomic is used: nothing depends on scheduling.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -26,6 +28,7 @@
 #include "../dronerl_learn_common.h"
 #include "../largelearn/dronerl_largelearn_chain.h"
 #include "dronerl_per_layout.h"
+#include "dronerl_per_chain.h"
 
 // every product and sum rounds on its own (no FMA contraction): the order tests/_per_ref.py restates
 #pragma clang fp contract(off)
@@ -55,140 +58,18 @@ __global__ void __launch_bounds__(kThreads) drl_per_mark_kernel(TreeArgs t, int6
 __global__ void __launch_bounds__(kRebuildThreads) drl_per_rebuild_kernel(float* __restrict__ tree, int64_t root0,
                                                                           int n) {
     __shared__ __attribute__((aligned(16))) float heap[2 * kRun];
-    const int tid = threadIdx.x;
-    const int64_t root = root0 + blockIdx.x;
-    for (int i = tid; i < n; i += kRebuildThreads) heap[n + i] = tree[root * n + i];
-    __syncthreads();
-    for (int w = n >> 1; w >= 1; w >>= 1) {  // the level of w nodes: heap [w, 2w), the tree's [root * w, (root + 1) * w)
-        for (int i = tid; i < w; i += kRebuildThreads) {
-            const ll::ll_f2 c = *reinterpret_cast<const ll::ll_f2*>(heap + 2 * (w + i));
-            const float v = c.x + c.y;
-            heap[w + i] = v;
-            tree[root * w + i] = v;
-        }
-        __syncthreads();
-    }
+    rebuild_body(tree, root0 + blockIdx.x, n, heap);
 }
 
-// ---- the sampler -----------------------------------------------------------------------------------------------
-// Row b of B: m = ((b + u) / B) * tree[1] with u the row's hash in [0, 1); the descent goes left when the right
-// child is 0.0 or m < left, so it stays inside nodes of positive value whatever the rounding does to m.
+// ---- the sampler (sample_body, dronerl_per_chain.h) ------------------------------------------------------------
 __global__ void __launch_bounds__(kSampleThreads) drl_per_sample_kernel(TreeArgs t, SampleArgs s,
                                                                         const DqnCounters* __restrict__ ctr) {
     __shared__ __attribute__((aligned(16))) float top[kTop];
     __shared__ uint32_t wmax_bits;
-    const int tid = threadIdx.x;
-    const float* __restrict__ tree = t.tree;
-    const int n_top = (int)(2 * t.P < kTop ? 2 * t.P : kTop);
-    for (int i = tid; i < n_top; i += kSampleThreads) top[i] = tree[i];
-    if (tid == 0) wmax_bits = 0u;
-    __syncthreads();
-    const int32_t step = ctr->step;
-    const int B = t.batch;
-    const float root = top[1];
-    int64_t idx[kSampleRows];
-    float m[kSampleRows];
-#pragma unroll
-    for (int r = 0; r < kSampleRows; ++r) {
-        const int b = tid + r * kSampleThreads;
-        const uint64_t h = splitmix64(s.seed ^ splitmix64(((uint64_t)(uint32_t)step << 16) | (uint64_t)b));
-        const float u = (float)(h >> 40) * (1.0f / 16777216.0f);
-        m[r] = ((float)b + u) / (float)B * root;
-        idx[r] = 1;
-    }
-    // the rows of a thread descend level by level together: their loads are independent and stay in flight
-    for (int lvl = 0; lvl < t.logP; ++lvl) {
-        const bool in_lds = ((int64_t)2 << lvl) < kTop;  // the children's level lies below kTop: uniform
-#pragma unroll
-        for (int r = 0; r < kSampleRows; ++r) {
-            if (tid + r * kSampleThreads >= B) continue;
-            const int64_t c = 2 * idx[r];
-            const ll::ll_f2 lr = in_lds ? *reinterpret_cast<const ll::ll_f2*>(top + c)
-                                        : *reinterpret_cast<const ll::ll_f2*>(tree + c);
-            if (lr.y == 0.0f || m[r] < lr.x) {
-                idx[r] = c;
-            } else {
-                m[r] = m[r] - lr.x;
-                idx[r] = c + 1;
-            }
-        }
-    }
-    double beta = s.beta0;
-    if (s.beta_steps > 0) {
-        const double f = (double)step / (double)s.beta_steps;
-        beta = s.beta0 + (1.0 - s.beta0) * (f < 1.0 ? f : 1.0);
-    }
-    float w[kSampleRows];
-#pragma unroll
-    for (int r = 0; r < kSampleRows; ++r) {
-        const int b = tid + r * kSampleThreads;
-        w[r] = 0.0f;
-        if (b >= B) continue;
-        const float leaf = tree[idx[r]];
-        w[r] = (float)pow((double)s.size * ((double)leaf / (double)root), -beta);
-        // (a pad leaf is 0.0 and never entered; the clamp only keeps a tree the caller filled wrongly from naming
-        // a slot outside the ring)
-        const int64_t slot = idx[r] - t.P;
-        t.slots[b] = slot < t.capacity ? slot : t.capacity - 1;
-        atomicMax(&wmax_bits, __float_as_uint(w[r]));  // (LDS; the weights are positive floats)
-    }
-    __syncthreads();
-    const float wmax = __uint_as_float(wmax_bits);
-    if (tid == 0) *t.wmax = wmax;
-#pragma unroll
-    for (int r = 0; r < kSampleRows; ++r) {
-        const int b = tid + r * kSampleThreads;
-        if (b < B) t.weights[b] = w[r] / wmax;
-    }
+    sample_body(t, s, ctr->step, top, &wmax_bits);
 }
 
-// ---- the learner -----------------------------------------------------------------------------------------------
-// 1. The rows: ll::rows_body with the drawn slot in place of dq_sample.
-template <class A>
-__device__ __forceinline__ void per_rows_body(const ll::Plan& P, const A& a, int B, int64_t e) {
-    const int64_t per = (int64_t)B * P.in4;
-    if (e >= 2 * per) return;
-    const int n = e >= per ? 1 : 0;
-    const int64_t r = e - n * per;
-    const int b = (int)(r / P.in4), k = (int)(r - (int64_t)b * P.in4);
-    const int64_t s = a.slots[b];
-    a.scratch[ll::x_word(P, n, b, k)] = k < P.in[0] ? dq_input(a, n ? a.r_next : a.r_obs, s, k) : 0.0f;
-    if (n == 0 && k == 0) {
-        reinterpret_cast<int32_t*>(a.scratch)[P.act_off + b] = a.r_act[s];
-        a.scratch[P.rew_off + b] = a.r_rew[s];
-        a.scratch[P.done_off + b] = a.r_done[s] ? 1.0f : 0.0f;
-    }
-}
-
-// 3. The TD error of row b: ll::td_body with the row's importance weight w on its squared error and on the Q
-// head's delta; |d| is kept for the priority kernel and the slot's leaf zeroed, so that the integer max there
-// starts from 0.0 (a slot drawn by several rows is zeroed by each of them: the same store).
-template <class A>
-__device__ __forceinline__ void per_td_body(const ll::Plan& P, const A& a, int B, int b) {
-    if (b >= B) return;
-    const int L = P.n_layers, NA = P.out[L - 1];
-    const float* q = a.scratch + ll::h_word(P, 0, L - 1, b, 0);
-    const float* qt = a.scratch + ll::h_word(P, 1, L - 1, b, 0);
-    float mx = qt[0];
-    for (int j = 1; j < NA; ++j) mx = qt[j] > mx ? qt[j] : mx;  // jnp.max
-    const int act = reinterpret_cast<const int32_t*>(a.scratch)[P.act_off + b];
-    const float rew = a.scratch[P.rew_off + b];
-    const float notdone = a.scratch[P.done_off + b] != 0.0f ? 0.0f : 1.0f;
-    const float td = rew + (a.gamma * mx) * notdone;
-    const bool ok = act >= 0 && act < NA;
-    float qa = td;
-    for (int j = 0; j < NA; ++j)
-        if (ok && j == act) qa = q[j];
-    const float d = qa - td;
-    const float w = a.weights[b];
-    a.scratch[P.sq_off + b] = w * (d * d);
-    float* dq = a.scratch + ll::d_word(P, L - 1, b, 0);
-    const float g = w * ((d + d) / (float)B);
-    for (int j = 0; j < P.ld[L - 1]; ++j) dq[j] = (ok && j == act) ? g : 0.0f;
-    a.absd[b] = __builtin_fabsf(d);
-    a.leaves[a.slots[b]] = 0.0f;
-}
-
+// ---- the learner (per_rows_body, per_td_body, priority_body: dronerl_per_chain.h) ------------------------------
 __global__ void __launch_bounds__(kThreads) drl_dqn_per_rows_kernel(LearnArgs args) {
     (void)args;
     const LearnArgs& a = *(const LearnArgs*)__builtin_amdgcn_kernarg_segment_ptr();
@@ -208,25 +89,12 @@ __global__ void __launch_bounds__(kThreads) drl_dqn_per_td_kernel(LearnArgs args
     per_td_body(a.P, a, a.P.batch, (int)(blockIdx.x * kThreads + threadIdx.x));
 }
 
-// 6. The priorities: row b's p = (|d| + eps)^alpha (double, rounded once; at most 2^64, which a NaN becomes too)
-// into its slot's leaf, which the TD kernel zeroed: the largest over the rows that drew the slot.  pmax likewise
-// (a workgroup's largest first, in LDS).
+// 6. The priorities (priority_body): each drawn leaf raised to its rows' largest new priority, and pmax.
 __global__ void __launch_bounds__(kThreads) drl_dqn_per_priority_kernel(LearnArgs args) {
     (void)args;
     const LearnArgs& a = *(const LearnArgs*)__builtin_amdgcn_kernarg_segment_ptr();
     __shared__ uint32_t wg_max;
-    if (threadIdx.x == 0) wg_max = 0u;
-    __syncthreads();
-    const int b = (int)(blockIdx.x * kThreads + threadIdx.x);
-    if (b < a.P.batch) {
-        float p = (float)pow((double)a.absd[b] + a.per_eps, a.alpha);
-        if (!(p <= kMaxPriority)) p = kMaxPriority;
-        const uint32_t bits = __float_as_uint(p);
-        atomicMax(reinterpret_cast<uint32_t*>(a.leaves + a.slots[b]), bits);
-        atomicMax(&wg_max, bits);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && wg_max) atomicMax(reinterpret_cast<uint32_t*>(a.pmax), wg_max);
+    priority_body(a, a.P.batch, (int)(blockIdx.x * kThreads + threadIdx.x), &wg_max);
 }
 
 __global__ void __launch_bounds__(ll::kTileThreads) drl_dqn_per_backward_kernel(LearnArgs args, int l) {

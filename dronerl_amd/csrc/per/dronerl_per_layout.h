@@ -100,7 +100,7 @@ struct TreeArgs {
     int32_t batch, logP;
 };
 
-inline TreeArgs tree_args(const Plan& p, void* d_per) {
+DRL_PER_HD TreeArgs tree_args(const Plan& p, void* d_per) {
     uint8_t* base = static_cast<uint8_t*>(d_per);
     TreeArgs t;
     t.tree = reinterpret_cast<float*>(base + p.pub.tree_off);

@@ -30,7 +30,7 @@ import torch
 
 from ._native import DroneRLError, lib
 from .dqn import (INPUTS, NUM_ACTIONS, ConvQNetwork, DQNHParams, DrlConvnetDesc, DrlConvnetDqnLayout, DrlDqnHParams,
-                  DrlDqnLayout, DrlReplay, DrlWidenetDesc, QNetwork, WideQNetwork, _bind, _bind_convnet, _check, _on,
+                  DrlDqnLayout, DrlPerHParams, DrlPerLayout, DrlReplay, DrlWidenetDesc, QNetwork, WideQNetwork, _bind, _bind_convnet, _check, _on,
                   _stream, _vp, convnet_desc, flax_kernel_init, is_wide)
 from .params import EnvParams
 
@@ -517,6 +517,188 @@ class ConvPopulationDQN(PopulationDQN):
         save_conv(path, ws[:nc], bs[:nc], ws[nc:], bs[nc:], self.obs_shape, format=format, **kw)
 
 
+class DrlPopPerLayout(ctypes.Structure):
+    _fields_ = [("member", DrlPerLayout), ("member_stride", ctypes.c_int64), ("hparams_off", ctypes.c_int64),
+                ("hparams_stride", ctypes.c_int64), ("bytes", ctypes.c_int64), ("members", ctypes.c_int32),
+                ("max_batch", ctypes.c_int32)]
+
+
+def _bind_pop_per(L):
+    if getattr(L, "_pop_per_ready", False):
+        return L
+    i32, i64 = ctypes.c_int32, ctypes.c_int64
+    D, R = ctypes.POINTER(DrlWidenetDesc), ctypes.POINTER(DrlReplay)
+    sig = {
+        "drl_pop_per_layout_query": [i32, i64, i32, ctypes.POINTER(DrlPopPerLayout)],
+        "drl_pop_per_init": [i32, i64, i32, ctypes.POINTER(DrlPerHParams), _vp, _vp],
+        "drl_pop_per_mark_new": [i32, i64, i32, _vp, i64, i64, _vp],
+        "drl_pop_per_rebuild": [i32, i64, i32, _vp, _vp],
+        "drl_pop_per_sample": [D, i32, i32, _vp, _vp, i64, i64, _vp],
+        "drl_pop_per_train": [D, i32, i32, _vp, R, i64, _vp, _vp],
+    }
+    for name, args in sig.items():
+        f = getattr(L, name)
+        f.argtypes = args
+        f.restype = ctypes.c_int
+    L._pop_per_ready = True
+    return L
+
+
+PER_KEYS = ("alpha", "beta0", "beta_steps", "eps")
+
+
+def per_record(per: Optional[dict] = None) -> dict:
+    """A member's PER hyperparameters (dqn.PrioritizedReplay's keywords and
+    defaults), validated by name."""
+    rec = dict(alpha=0.6, beta0=0.4, beta_steps=0, eps=1e-6)
+    for k, v in (per or {}).items():
+        if k not in PER_KEYS:
+            raise ValueError(f"per: {k} is not one of {', '.join(PER_KEYS)}")
+        rec[k] = v
+    if not rec["alpha"] >= 0:
+        raise ValueError("alpha must be >= 0")
+    if not 0 <= rec["beta0"] <= 1:
+        raise ValueError("beta0 must be in [0, 1]")
+    if rec["beta_steps"] < 0:
+        raise ValueError("beta_steps must be >= 0")
+    if not rec["eps"] >= 0:
+        raise ValueError("eps must be >= 0")
+    return dict(alpha=float(rec["alpha"]), beta0=float(rec["beta0"]), beta_steps=int(rec["beta_steps"]),
+                eps=float(rec["eps"]))
+
+
+class PrioritizedPopulationReplay:
+    """Proportional prioritized replay around a PopulationReplay, which stays
+    as it is: a priority sum tree per member over its ring, in one allocation
+    (drl_pop_per_*; include/dronerl.h describes the block), each member with
+    its own alpha, beta0, beta_steps and eps.  `add` is the population's add
+    followed by drl_pop_per_mark_new for the same cursor and count: the new
+    rows enter every member's tree with that member's largest priority so far.
+
+    pers: one dict alpha / beta0 / beta_steps / eps per member (missing keys:
+    dqn.PrioritizedReplay's defaults).  max_batch: the population's.  Views of
+    member m's block: tree(m) (f32 [2P]), pmax(m), wmax(m) (f32 [1]),
+    slots(m) (int64 [max_batch]), weights(m) and abs_td(m) (f32 [max_batch]);
+    a member's step fills the first batch_m entries."""
+
+    def __init__(self, replay: PopulationReplay, pers: Sequence[dict], max_batch: int, guard_bytes: int = 0):
+        if not isinstance(replay, PopulationReplay):
+            raise ValueError("PrioritizedPopulationReplay wraps a population.PopulationReplay")
+        self.replay, self.L = replay, _bind_pop_per(replay.L)
+        self.pers = [per_record(p) for p in pers]
+        if len(self.pers) != replay.members:
+            raise ValueError("pers: one dict of PER hyperparameters per member")
+        self.max_batch = int(max_batch)
+        lay = DrlPopPerLayout()
+        if self.L.drl_pop_per_layout_query(replay.members, replay.capacity, self.max_batch, ctypes.byref(lay)):
+            raise ValueError(self.L.drl_last_error().decode())
+        self.layout = lay
+        dev = replay.obs.device
+        self._alloc = torch.zeros(lay.bytes + int(guard_bytes), dtype=torch.uint8, device=dev)
+        self.block = self._alloc[:lay.bytes]
+        self._hp = (DrlPerHParams * replay.members)(*[DrlPerHParams(p["alpha"], p["beta0"], p["beta_steps"], p["eps"])
+                                                      for p in self.pers])
+        _check(self.L, self.L.drl_pop_per_init(replay.members, replay.capacity, self.max_batch, self._hp,
+                                               _vp(self.block.data_ptr()), _stream(dev)))
+        if replay.size:  # the rows written before the trees existed: the ring's contents as wrapped
+            self._mark(0 if replay.size < replay.capacity else replay.cursor, replay.size)
+
+    members = property(lambda self: self.replay.members)
+    capacity = property(lambda self: self.replay.capacity)
+    size = property(lambda self: self.replay.size)
+    cursor = property(lambda self: self.replay.cursor)
+    obs = property(lambda self: self.replay.obs)
+
+    def ring(self, m: int) -> dict:
+        return self.replay.ring(m)
+
+    def _mark(self, cursor: int, count: int):
+        _check(self.L, self.L.drl_pop_per_mark_new(self.members, self.capacity, self.max_batch,
+                                                   _vp(self.block.data_ptr()), int(cursor), int(count),
+                                                   _stream(self.replay.obs.device)))
+
+    def add(self, code_prev: torch.Tensor, actions: torch.Tensor, rewards: torch.Tensor, code: torch.Tensor,
+            dones: torch.Tensor):
+        """PopulationReplay.add, then the new rows' leaves = the member's pmax."""
+        cursor = self.replay.cursor
+        self.replay.add(code_prev, actions, rewards, code, dones)
+        self._mark(cursor, code.shape[0] // self.members)
+
+    def rebuild(self):
+        """Every internal node of every member's tree from its leaves (drl_pop_per_rebuild)."""
+        _check(self.L, self.L.drl_pop_per_rebuild(self.members, self.capacity, self.max_batch,
+                                                  _vp(self.block.data_ptr()), _stream(self.replay.obs.device)))
+
+    def _view(self, m: int, off: int, n: int, dt, size: int) -> torch.Tensor:
+        if not 0 <= m < self.members:
+            raise IndexError("member out of range")
+        at = m * self.layout.member_stride + off
+        return self.block[at:at + n * size].view(dt)
+
+    def member_block(self, m: int) -> torch.Tensor:
+        """Member m's prioritized block (uint8 view): drl_per_layout_query's layout."""
+        return self._view(m, 0, self.layout.member.bytes, torch.uint8, 1)
+
+    def tree(self, m: int) -> torch.Tensor:
+        return self._view(m, self.layout.member.tree_off, 2 * self.layout.member.leaves, torch.float32, 4)
+
+    def pmax(self, m: int) -> torch.Tensor:
+        return self._view(m, self.layout.member.pmax_off, 1, torch.float32, 4)
+
+    def wmax(self, m: int) -> torch.Tensor:
+        return self._view(m, self.layout.member.wmax_off, 1, torch.float32, 4)
+
+    def slots(self, m: int) -> torch.Tensor:
+        return self._view(m, self.layout.member.slots_off, self.max_batch, torch.int64, 8)
+
+    def weights(self, m: int) -> torch.Tensor:
+        return self._view(m, self.layout.member.weights_off, self.max_batch, torch.float32, 4)
+
+    def abs_td(self, m: int) -> torch.Tensor:
+        return self._view(m, self.layout.member.absd_off, self.max_batch, torch.float32, 4)
+
+
+class PrioritizedPopulationDQN(PopulationDQN):
+    """PopulationDQN on prioritized rows (drl_pop_per_train): the same block,
+    act and launch chain; `train(replay)` takes a PrioritizedPopulationReplay
+    and every member that holds a batch rebuilds its tree, draws by priority,
+    trains with each row's importance weight on its squared error and on the
+    Q head's delta, and writes (|td error| + eps) ** alpha back to the drawn
+    slots -- PrioritizedDQNLearner's step bit for bit at the widths both take,
+    whoever shares the population; stream-ordered, graph-capturable, a launch
+    count that does not depend on the number of members."""
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.L = _bind_pop_per(self.L)
+
+    def _check_replay(self, replay):
+        if not isinstance(replay, PrioritizedPopulationReplay):
+            raise ValueError("PrioritizedPopulationDQN.train takes a PrioritizedPopulationReplay")
+        if replay.obs.device != self.device or replay.members != self.members:
+            raise ValueError("the replay must be on the population's device and hold one ring per member")
+        if replay.max_batch != self.max_batch:
+            raise ValueError(f"the prioritized replay is laid out for max_batch {replay.max_batch}, the population "
+                             f"for {self.max_batch}")
+
+    def train(self, replay: PrioritizedPopulationReplay):
+        """One prioritized learner block of every member on its ring: member
+        m trains iff replay.size >= its batch (decided on the device)."""
+        self._check_replay(replay)
+        _check(self.L, self.L.drl_pop_per_train(ctypes.byref(self.desc), self.members, self.max_batch,
+                                                _vp(self.block.data_ptr()), ctypes.byref(replay.replay._c),
+                                                replay.size, _vp(replay.block.data_ptr()), _stream(self.device)))
+
+    def sample(self, replay: PrioritizedPopulationReplay):
+        """drl_pop_per_sample from the trees as they stand (replay.rebuild()
+        first): the slots, weights and wmax of every member that holds a
+        batch, for the step its counters hold."""
+        self._check_replay(replay)
+        _check(self.L, self.L.drl_pop_per_sample(ctypes.byref(self.desc), self.members, self.max_batch,
+                                                 _vp(self.block.data_ptr()), _vp(replay.block.data_ptr()),
+                                                 replay.capacity, replay.size, _stream(self.device)))
+
+
 @dataclass
 class PopulationResult:
     env: object
@@ -530,7 +712,8 @@ def train_population(params: EnvParams, members: Sequence[DQNHParams], envs_per_
                      hidden: Sequence[int] = (128, 64), reset_env_every: int = 100, memory_size: int = 100_000,
                      seed: int = 0, env_offset: int = 0, action_seed: int = 2024, act_seed: int = 7, device=None,
                      seeds: Optional[Sequence[int]] = None, on_step=None, network_type: str = "dense",
-                     conv_layers=None, conv_dense_layers: Sequence[int] = (), **pop_kw) -> PopulationResult:
+                     conv_layers=None, conv_dense_layers: Sequence[int] = (), per: Optional[Sequence[dict]] = None,
+                     **pop_kw) -> PopulationResult:
     """`train`'s loop for a population: per step the population act, one env
     step over all P*E envs writing drone 0's next policy code, the add into
     the members' rings, the members' learner blocks, and a reset of every env
@@ -539,13 +722,23 @@ def train_population(params: EnvParams, members: Sequence[DQNHParams], envs_per_
     `seed` for all).  on_step(t, pop, replay, acts, rewards, dones): called
     between step t's add and its train (tests).  network_type "conv": a
     ConvPopulationDQN of conv_layers (default train_jax.py's one 3x3 layer of
-    8 channels, padding 1) and conv_dense_layers; `hidden` is then unused."""
+    8 channels, padding 1) and conv_dense_layers; `hidden` is then unused.
+    per: one dict alpha / beta0 / beta_steps / eps per member: a
+    PrioritizedPopulationDQN on a PrioritizedPopulationReplay (dense nets
+    only); None: uniform replay."""
     from .env import BatchedDeliveryDrones
     if num_steps < 1 or reset_env_every < 1:
         raise ValueError("num_steps and reset_env_every must be >= 1")
     if network_type not in ("dense", "conv"):
         raise ValueError("network_type must be 'dense' or 'conv'")
     members = list(members)
+    if per is not None:
+        if network_type == "conv":
+            raise ValueError("train_population(per=...) with network_type='conv' is not implemented: a prioritized "
+                             "population trains dense nets only")
+        per = list(per)
+        if len(per) != len(members):
+            raise ValueError("per: one dict of PER hyperparameters per member")
     P, E = len(members), int(envs_per_member)
     env = BatchedDeliveryDrones(params, P * E, device=device, env_offset=env_offset)
     env.reset(seed=seed)
@@ -557,9 +750,13 @@ def train_population(params: EnvParams, members: Sequence[DQNHParams], envs_per_
         W = 2 * r + 1
         pop = ConvPopulationDQN((W, W, 6), conv_layers if conv_layers is not None else TRAIN_JAX_CONV_LAYERS,
                                 tuple(conv_dense_layers), members, E, device=dev, seeds=seeds, **pop_kw)
+    elif per is not None:
+        pop = PrioritizedPopulationDQN(D, hidden, members, E, device=dev, seeds=seeds, **pop_kw)
     else:
         pop = PopulationDQN(D, hidden, members, E, device=dev, seeds=seeds, **pop_kw)
     rb = PopulationReplay(P, memory_size, r, device=dev)
+    if per is not None:
+        rb = PrioritizedPopulationReplay(rb, per, pop.max_batch)
     code = [env.new_code(), env.new_code()]
     env.get_code(out=code[0])
     acts = torch.empty((P * E, N), dtype=torch.int32, device=dev)

@@ -1018,6 +1018,70 @@ int drl_pop_sample_rows(const drl_widenet_desc* d, int32_t members, int32_t max_
                         int64_t* d_slots, hipStream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Prioritized replay for a population of dense DQN agents: every member
+ * owns a priority tree over its ring and its own drl_per_hparams (alpha,
+ * beta0, beta_steps, eps), so one population sweeps them.  The members
+ * sample, train and write their priorities back in the population's chain:
+ * the launch count of a step does not depend on `members`.  A member's
+ * arithmetic is drl_dqn_per_train's bit for bit at the widths both take (the
+ * same device bodies: rebuild, the stratified draw written above
+ * drl_per_sample with the member's batch, sample_seed, its own counter's step
+ * and its record's beta, the weighted TD error, the priority update) and does
+ * not depend on which other members share the population.  The description,
+ * the population block, the rings, drl_pop_act and drl_pop_replay_add are
+ * drl_pop_*'s, unchanged; hidden widths up to DRL_WIDENET_MAX_WIDTH.
+ *   The block (device, caller-owned, 16-B aligned, drl_pop_per_layout.bytes):
+ *   `members` prioritized blocks member_stride bytes apart, each laid out
+ *   exactly as drl_per_layout_query(capacity, max_batch) lays out one agent
+ *   (`member`: tree[2P], pmax, wmax, slots, weights, |d|; member m uses the
+ *   first batch_m entries of the three arrays), then one record of PER
+ *   hyperparameters per member at hparams_off.  The rings, the cursor and the
+ *   size are the population's: one cursor and one size for all members.
+ *   A member trains iff size >= its batch (decided on the device).  One that
+ *   does not is skipped by rebuild, sample and the chain up to the backward:
+ *   its tree, pmax, slots and weights are left alone, as drl_dqn_per_train
+ *   leaves them; it still blends its target when due, decays epsilon and
+ *   advances its step.
+ * No call but drl_pop_per_init synchronises or reads host hyperparameters;
+ * nothing is allocated, no workgroup waits for another, no float atomic is
+ * used: mark, rebuild, sample and train are graph-capturable.  Every argument
+ * is validated before any device work.
+ * ------------------------------------------------------------------------ */
+typedef struct drl_pop_per_layout {
+    drl_per_layout member;   /* one member's block (offsets from the member's start) */
+    int64_t member_stride;   /* bytes from member m's block to member m+1's */
+    int64_t hparams_off;     /* bytes: the PER records (opaque) */
+    int64_t hparams_stride;
+    int64_t bytes;
+    int32_t members, max_batch;
+} drl_pop_per_layout;
+/* Host only.  members in [1, DRL_POP_MAX_MEMBERS], capacity in [1, DRL_PER_MAX_CAPACITY], max_batch in
+ * [1, DRL_DQN_LARGE_MAX_BATCH]. */
+int drl_pop_per_layout_query(int32_t members, int64_t capacity, int32_t max_batch, drl_pop_per_layout* layout);
+/* ph: a HOST array of `members` drl_per_hparams (drl_per_hparams' ranges).  Uploads the records (synchronises
+ * `stream`), then zeroes every member's tree, pmax = 1. */
+int drl_pop_per_init(int32_t members, int64_t capacity, int32_t max_batch, const drl_per_hparams* ph, void* d_pper,
+                     hipStream_t stream);
+/* After drl_pop_replay_add with the same cursor and count = envs_per_member: the leaves of slots
+ * [cursor, cursor + count) mod capacity of every member = that member's own pmax (count > capacity marks every
+ * slot). */
+int drl_pop_per_mark_new(int32_t members, int64_t capacity, int32_t max_batch, void* d_pper, int64_t cursor,
+                         int64_t count, hipStream_t stream);
+/* Every internal node of every member's tree from its leaves (two launches at most). */
+int drl_pop_per_rebuild(int32_t members, int64_t capacity, int32_t max_batch, void* d_pper, hipStream_t stream);
+/* drl_per_sample for every member with size >= its batch, from rebuilt trees with positive roots: the member's
+ * slots, weights (its first batch_m entries; the rest untouched) and wmax for the step its own counters hold.
+ * size in [1, capacity]. */
+int drl_pop_per_sample(const drl_widenet_desc* d, int32_t members, int32_t max_batch, const void* d_pop, void* d_pper,
+                       int64_t capacity, int64_t size, hipStream_t stream);
+/* drl_pop_train on prioritized rows (its arguments; d_pper laid out for (members, r->capacity, max_batch)): one
+ * drl_dqn_per_train step of every member without the re-pack -- rebuild, sample, the rows at the drawn slots,
+ * each layer's forward of both nets, the weighted TD error, the priority update into the member's leaves and
+ * pmax, each layer's backward, the update (with the target blend of members that do not train), the counters. */
+int drl_pop_per_train(const drl_widenet_desc* d, int32_t members, int32_t max_batch, void* d_pop, const drl_replay* r,
+                      int64_t size, void* d_pper, hipStream_t stream);
+
+/* ------------------------------------------------------------------------
  * A population of conv DQN agents (run_jax_sweep.py draws network_type from
  * ['dense', 'conv']): the five drl_pop_* calls above for a drl_convnet_desc
  * with input DRL_QNET_INPUT_CODE (a 5x5, 7x7 or 9x9 window; every other
