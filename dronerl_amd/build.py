@@ -38,9 +38,11 @@ SOURCES = [os.path.join(CSRC, "dronerl_kernels.hip"), os.path.join(CSRC, "droner
            os.path.join(CSRC, "convselfplay", "dronerl_convselfplay.hip"),
            os.path.join(CSRC, "convselfplay", "dronerl_convselfplay_api.cpp"),
            os.path.join(CSRC, "per", "dronerl_per.hip"), os.path.join(CSRC, "per", "dronerl_per_api.cpp"),
-           os.path.join(CSRC, "perpop", "dronerl_perpop.hip"), os.path.join(CSRC, "perpop", "dronerl_perpop_api.cpp")]
+           os.path.join(CSRC, "perpop", "dronerl_perpop.hip"), os.path.join(CSRC, "perpop", "dronerl_perpop_api.cpp"),
+           os.path.join(CSRC, "convper", "dronerl_convper.hip"),
+           os.path.join(CSRC, "convper", "dronerl_convper_api.cpp")]
 DEPS = SOURCES + [os.path.join(CSRC, "dronerl_internal.h"), os.path.join(CSRC, "dronerl_act_common.h"),
-                  os.path.join(CSRC, "dronerl_learn_common.h"),
+                  os.path.join(CSRC, "dronerl_learn_common.h"), os.path.join(CSRC, "dronerl_learn_args.h"),
                   os.path.join(CSRC, "convlearn", "dronerl_convlearn_layout.h"),
                   os.path.join(CSRC, "convlearn", "dronerl_convlearn_rows.h"),
                   os.path.join(CSRC, "convlarge", "dronerl_convlarge_layout.h"),
@@ -57,6 +59,8 @@ DEPS = SOURCES + [os.path.join(CSRC, "dronerl_internal.h"), os.path.join(CSRC, "
                   os.path.join(CSRC, "per", "dronerl_per_layout.h"),
                   os.path.join(CSRC, "per", "dronerl_per_chain.h"),
                   os.path.join(CSRC, "perpop", "dronerl_perpop_layout.h"),
+                  os.path.join(CSRC, "convper", "dronerl_convper_layout.h"),
+                  os.path.join(CSRC, "convper", "dronerl_convper_chain.h"),
                   os.path.join(CSRC, "widenet", "dronerl_widenet_layout.h"),
                   os.path.join(CSRC, "evalcode", "dronerl_evalcode_layout.h"),
                   os.path.join(CSRC, "convnet", "dronerl_convnet_layout.h"), os.path.join(REPO, "include", "dronerl.h")]

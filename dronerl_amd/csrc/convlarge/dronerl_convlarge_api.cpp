@@ -9,6 +9,7 @@
 
 #include "../../../include/dronerl.h"
 #include "../dronerl_internal.h"
+#include "../dronerl_learn_args.h"
 #include "dronerl_convlarge_layout.h"
 
 extern "C" __attribute__((visibility("hidden"))) int drl_internal_fail(const char* msg);
@@ -70,55 +71,12 @@ int drl_convnet_dqn_large_train(const drl_convnet_desc* d, const drl_dqn_hparams
     drl::cl::LearnArgs& a = full.a;
     a.P = plan.c;
     const drl::cl::Plan& P = a.P;
-    if (h->target_update_interval < 1 || h->epsilon_decay_every < 1)
-        return fail("target_update_interval and epsilon_decay_every must be >= 1");
-    if (!(h->beta1 >= 0.0 && h->beta1 < 1.0 && h->beta2 >= 0.0 && h->beta2 < 1.0))
-        return fail("beta1 and beta2 must be in [0, 1)");
-    if (!d_agent || (uintptr_t)d_agent % 16) return fail("the agent block must be a 16-byte aligned device pointer");
-    if (!d_packed || (uintptr_t)d_packed % 16) return fail("packed buffer must be a 16-byte aligned device pointer");
-    if (!r || !r->obs || !r->next_obs || !r->actions || !r->rewards || !r->dones) return fail("replay buffers are NULL");
+    if (const char* msg = drl::check_learn_call(h, d_agent, d_packed, r)) return fail(msg);
     if (r->capacity < 1 || r->capacity >= ((int64_t)1 << 31)) return fail("replay capacity must be in [1, 2^31)");
     if (size < 0 || size > r->capacity) return fail("size must be in [0, capacity]");
-    if (P.code_w) {
-        if ((int64_t)r->obs_floats * 4 != drl::lay::code_bytes(P.code_w))
-            return fail("a DRL_QNET_INPUT_CODE net's replay rows are policy codes (drl_policy_code_bytes / 4 words)");
-    } else if (r->obs_floats < P.in) {
-        return fail("replay obs_floats < window * window * 6");
-    }
-    if ((uintptr_t)r->obs % 4 || (uintptr_t)r->next_obs % 4) return fail("replay rows must be 4-byte aligned");
-    uint8_t* base = static_cast<uint8_t*>(d_agent);
-    a.trained = size >= h->batch;  // buffers.py:92-93 can_sample
-    a.code_w = P.code_w;
-    a.online = reinterpret_cast<float*>(base + P.pub.online_off);
-    a.target = reinterpret_cast<float*>(base + P.pub.target_off);
-    a.adam_m = reinterpret_cast<float*>(base + P.pub.m_off);
-    a.adam_v = reinterpret_cast<float*>(base + P.pub.v_off);
-    a.ctr = reinterpret_cast<drl::DqnCounters*>(base + P.pub.counters_off);
-    a.scratch = reinterpret_cast<float*>(base + P.pub.scratch_off);
-    a.r_obs = reinterpret_cast<const uint32_t*>(r->obs);
-    a.r_next = reinterpret_cast<const uint32_t*>(r->next_obs);
-    a.row_words = r->obs_floats;
-    a.r_act = r->actions;
-    a.r_rew = r->rewards;
-    a.r_done = r->dones;
-    a.size = size;
-    a.seed = h->sample_seed;
-    // the python floats as jax's weak typing rounds them into f32 arithmetic
-    a.gamma = (float)h->gamma;
-    a.b1 = (float)h->beta1;
-    a.b2 = (float)h->beta2;
-    a.c1 = (float)(1.0 - h->beta1);
-    a.c2 = (float)(1.0 - h->beta2);
-    a.adam_eps = (float)h->adam_eps;
-    a.neg_lr = (float)(-h->learning_rate);
-    a.tau = (float)h->tau;
-    a.one_minus_tau = (float)(1.0 - h->tau);
-    a.eps_decay = (float)h->epsilon_decay;
-    a.eps_end = (float)h->epsilon_end;
-    a.b1d = h->beta1;
-    a.b2d = h->beta2;
-    a.target_every = h->target_update_interval;
-    a.eps_every = h->epsilon_decay_every;
+    if (const char* msg = drl::check_learn_rows(r, P.code_w, P.in, "replay obs_floats < window * window * 6"))
+        return fail(msg);
+    drl::fill_learn_args(a, P.pub, P.code_w, h, d_agent, r, size);
     // the act's image of the new online set: the pack kernel itself on the online set, so the image is a fresh
     // drl_convnet_pack's byte for byte; the counters kernel has stored the status vector's zeros, so a captured
     // call holds kernel nodes only (DESIGN.md §4 "Conv learner")

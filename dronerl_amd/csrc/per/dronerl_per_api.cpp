@@ -1,5 +1,5 @@
 // dronerl_per_api.cpp — C ABI of the prioritized replay and its learner (include/dronerl.h drl_per_*,
-// drl_dqn_per_train; kernels in dronerl_per.hip, the block's layout in dronerl_per_layout.h).
+// drl_dqn_per_train, drl_widenet_dqn_per_train; kernels in dronerl_per.hip, the block's layout in dronerl_per_layout.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -7,7 +7,9 @@
 
 #include "../../../include/dronerl.h"
 #include "../dronerl_internal.h"
+#include "../dronerl_learn_args.h"
 #include "../largelearn/dronerl_largelearn_layout.h"
+#include "../widenet/dronerl_widenet_layout.h"
 #include "dronerl_per_layout.h"
 
 extern "C" __attribute__((visibility("hidden"))) int drl_internal_fail(const char* msg);
@@ -35,11 +37,33 @@ int per_block(int64_t capacity, int32_t batch, void* d_per, drl::per::Plan* P) {
 }
 
 int per_hparams(const drl_per_hparams* ph) {
-    if (!ph) return fail("the prioritized replay's hparams are NULL");
-    if (!(ph->alpha >= 0.0)) return fail("alpha must be >= 0");
-    if (!(ph->beta0 >= 0.0 && ph->beta0 <= 1.0)) return fail("beta0 must be in [0, 1]");
-    if (ph->beta_steps < 0) return fail("beta_steps must be >= 0");
-    if (!(ph->eps >= 0.0)) return fail("eps must be >= 0");
+    if (const char* msg = drl::per::check_hparams(ph)) return fail(msg);
+    return 0;
+}
+
+// What drl_dqn_per_train and drl_widenet_dqn_per_train share behind their plans (a.P): every check of the
+// hyperparameters, the blocks and the ring, then the chain's arguments, the tree's view and the sampler's.
+int per_learn_args(drl::per::LearnArgs& a, int in_features, const drl_dqn_hparams* h, const drl_per_hparams* ph,
+                   void* d_agent, void* d_packed, const drl_replay* r, int64_t size, void* d_per,
+                   drl::per::TreeArgs* t, drl::per::SampleArgs* sa) {
+    const drl::ll::Plan& P = a.P;
+    if (per_hparams(ph)) return -1;
+    if (const char* msg = drl::check_learn_call(h, d_agent, d_packed, r)) return fail(msg);
+    drl::per::Plan T;
+    if (per_block(r->capacity, h->batch, d_per, &T)) return -1;
+    if (size < 0 || size > r->capacity) return fail("size must be in [0, capacity]");
+    if (const char* msg = drl::check_learn_rows(r, P.code_w, in_features, "replay obs_floats < in_features"))
+        return fail(msg);
+    drl::fill_learn_args(a, P.pub, P.code_w, h, d_agent, r, size);
+    *t = drl::per::tree_args(T, d_per);
+    a.slots = t->slots;
+    a.weights = t->weights;
+    a.absd = t->absd;
+    a.leaves = t->tree + t->P;
+    a.pmax = t->pmax;
+    a.alpha = ph->alpha;
+    a.per_eps = ph->eps;
+    *sa = drl::per::SampleArgs{h->sample_seed, size, ph->beta0, ph->beta_steps};
     return 0;
 }
 
@@ -98,66 +122,9 @@ int drl_dqn_per_train(const drl_qnet_desc* d, const drl_dqn_hparams* h, const dr
     if (!h) return fail("hparams is NULL");
     if (const char* msg = drl::ll::plan(L.n_layers, L.in, L.out, L.code_w, h->batch, &a.P)) return fail(msg);
     const drl::ll::Plan& P = a.P;
-    if (per_hparams(ph)) return -1;
-    if (h->target_update_interval < 1 || h->epsilon_decay_every < 1)
-        return fail("target_update_interval and epsilon_decay_every must be >= 1");
-    if (!(h->beta1 >= 0.0 && h->beta1 < 1.0 && h->beta2 >= 0.0 && h->beta2 < 1.0))
-        return fail("beta1 and beta2 must be in [0, 1)");
-    if (!d_agent || (uintptr_t)d_agent % 16) return fail("the agent block must be a 16-byte aligned device pointer");
-    if (!d_packed || (uintptr_t)d_packed % 16) return fail("packed buffer must be a 16-byte aligned device pointer");
-    if (!r || !r->obs || !r->next_obs || !r->actions || !r->rewards || !r->dones) return fail("replay buffers are NULL");
-    drl::per::Plan T;
-    if (per_block(r->capacity, h->batch, d_per, &T)) return -1;
-    if (size < 0 || size > r->capacity) return fail("size must be in [0, capacity]");
-    if (P.code_w) {
-        if ((int64_t)r->obs_floats * 4 != drl::lay::code_bytes(P.code_w))
-            return fail("a DRL_QNET_INPUT_CODE net's replay rows are policy codes (drl_policy_code_bytes / 4 words)");
-    } else if (r->obs_floats < d->in_features) {
-        return fail("replay obs_floats < in_features");
-    }
-    if ((uintptr_t)r->obs % 4 || (uintptr_t)r->next_obs % 4) return fail("replay rows must be 4-byte aligned");
-    uint8_t* base = static_cast<uint8_t*>(d_agent);
-    a.trained = size >= h->batch;  // buffers.py:92-93 can_sample
-    a.code_w = P.code_w;
-    a.online = reinterpret_cast<float*>(base + P.pub.online_off);
-    a.target = reinterpret_cast<float*>(base + P.pub.target_off);
-    a.adam_m = reinterpret_cast<float*>(base + P.pub.m_off);
-    a.adam_v = reinterpret_cast<float*>(base + P.pub.v_off);
-    a.ctr = reinterpret_cast<drl::DqnCounters*>(base + P.pub.counters_off);
-    a.scratch = reinterpret_cast<float*>(base + P.pub.scratch_off);
-    a.r_obs = reinterpret_cast<const uint32_t*>(r->obs);
-    a.r_next = reinterpret_cast<const uint32_t*>(r->next_obs);
-    a.row_words = r->obs_floats;
-    a.r_act = r->actions;
-    a.r_rew = r->rewards;
-    a.r_done = r->dones;
-    a.size = size;
-    a.seed = h->sample_seed;
-    // the python floats as jax's weak typing rounds them into f32 arithmetic (drl_dqn_large_train's)
-    a.gamma = (float)h->gamma;
-    a.b1 = (float)h->beta1;
-    a.b2 = (float)h->beta2;
-    a.c1 = (float)(1.0 - h->beta1);
-    a.c2 = (float)(1.0 - h->beta2);
-    a.adam_eps = (float)h->adam_eps;
-    a.neg_lr = (float)(-h->learning_rate);
-    a.tau = (float)h->tau;
-    a.one_minus_tau = (float)(1.0 - h->tau);
-    a.eps_decay = (float)h->epsilon_decay;
-    a.eps_end = (float)h->epsilon_end;
-    a.b1d = h->beta1;
-    a.b2d = h->beta2;
-    a.target_every = h->target_update_interval;
-    a.eps_every = h->epsilon_decay_every;
-    const drl::per::TreeArgs t = drl::per::tree_args(T, d_per);
-    a.slots = t.slots;
-    a.weights = t.weights;
-    a.absd = t.absd;
-    a.leaves = t.tree + t.P;
-    a.pmax = t.pmax;
-    a.alpha = ph->alpha;
-    a.per_eps = ph->eps;
-    const drl::per::SampleArgs sa = {h->sample_seed, size, ph->beta0, ph->beta_steps};
+    drl::per::TreeArgs t;
+    drl::per::SampleArgs sa;
+    if (per_learn_args(a, d->in_features, h, ph, d_agent, d_packed, r, size, d_per, &t, &sa)) return -1;
     // the act's image of the new online set, as drl_dqn_large_train refreshes it
     const float* w[drl::QN_MAX_LAYERS] = {};
     const float* b[drl::QN_MAX_LAYERS] = {};
@@ -172,6 +139,40 @@ int drl_dqn_per_train(const drl_qnet_desc* d, const drl_dqn_hparams* h, const dr
         return hip_fail(e, "drl_dqn_per_train launch");
     const hipError_t e = drl::launch_qnet_pack(pk, stream);
     return e == hipSuccess ? 0 : hip_fail((int)e, "drl_dqn_per_train pack launch");
+}
+
+// drl_dqn_per_train on a plan with the wide family's width limit (what drl_widenet_dqn_train is to
+// drl_dqn_large_train), then the wide pack kernel.
+int drl_widenet_dqn_per_train(const drl_widenet_desc* d, const drl_dqn_hparams* h, const drl_per_hparams* ph,
+                              void* d_agent, void* d_packed, const drl_replay* r, int64_t size, void* d_per,
+                              hipStream_t stream) {
+    drl::wn::PackArgs pk;
+    memset(&pk, 0, sizeof pk);
+    drl::per::LearnArgs a{};
+    if (const char* msg = drl::wn::layout(d, &pk.L)) return fail(msg);
+    if (!h) return fail("hparams is NULL");
+    int32_t in[drl::wn::kMaxLayers], out[drl::wn::kMaxLayers];
+    for (int l = 0; l < pk.L.n_layers; ++l) {
+        in[l] = pk.L.l[l].in;
+        out[l] = pk.L.l[l].out;
+    }
+    if (const char* msg = drl::ll::plan(pk.L.n_layers, in, out, pk.L.code_w, h->batch, &a.P, drl::wn::kMaxWidth))
+        return fail(msg);
+    const drl::ll::Plan& P = a.P;
+    drl::per::TreeArgs t;
+    drl::per::SampleArgs sa;
+    if (per_learn_args(a, d->in_features, h, ph, d_agent, d_packed, r, size, d_per, &t, &sa)) return -1;
+    // the act's image of the new online set, as drl_widenet_dqn_train refreshes it
+    for (int l = 0; l < P.n_layers; ++l) {
+        pk.w[l] = a.online + P.woff[l];
+        pk.b[l] = a.online + P.boff[l];
+    }
+    pk.packed = static_cast<uint32_t*>(d_packed);
+    a.pack_status = pk.packed + pk.L.status;
+    if (const int e = drl::per::launch_per_train(a, t, sa, stream); e != 0)
+        return hip_fail(e, "drl_widenet_dqn_per_train launch");
+    const int e = drl::wn::launch_widenet_pack(pk, stream);
+    return e == 0 ? 0 : hip_fail(e, "drl_widenet_dqn_per_train pack launch");
 }
 
 }  // extern "C"

@@ -82,6 +82,16 @@ inline const char* plan(int64_t capacity, int32_t batch, Plan* p) {
     return nullptr;
 }
 
+// The PER hyperparameters' ranges.  Returns nullptr, or the message for drl_last_error.
+inline const char* check_hparams(const drl_per_hparams* ph) {
+    if (!ph) return "the prioritized replay's hparams are NULL";
+    if (!(ph->alpha >= 0.0)) return "alpha must be >= 0";
+    if (!(ph->beta0 >= 0.0 && ph->beta0 <= 1.0)) return "beta0 must be in [0, 1]";
+    if (ph->beta_steps < 0) return "beta_steps must be >= 0";
+    if (!(ph->eps >= 0.0)) return "eps must be >= 0";
+    return nullptr;
+}
+
 // ---- the rebuild's launches ---------------------------------------------------------------------------------
 // the first launch: P / run workgroups, each over `run` leaves; a second one (one workgroup over the P / kRun
 // runs' roots) iff P > kRun

@@ -353,6 +353,8 @@ def _bind_convnet(L):
     }
     for call in ("layout_query", "init", "train", "sample_rows"):  # the same argument lists at batches up to 4096
         sig[f"drl_convnet_dqn_large_{call}"] = sig[f"drl_convnet_dqn_{call}"]
+    sig["drl_convnet_dqn_per_train"] = [D, ctypes.POINTER(DrlDqnHParams), ctypes.POINTER(DrlPerHParams), _vp, _vp,
+                                        ctypes.POINTER(DrlReplay), i64, _vp, _vp]
     for name, args in sig.items():
         f = getattr(L, name)
         f.argtypes = args
@@ -588,6 +590,8 @@ def _bind_widenet(L):
         "drl_widenet_dqn_init": [D, i32, _vp, f32, _vp],
         "drl_widenet_dqn_train": [D, ctypes.POINTER(DrlDqnHParams), _vp, _vp, ctypes.POINTER(DrlReplay), i64, _vp],
         "drl_widenet_dqn_sample_rows": [D, ctypes.POINTER(DrlDqnHParams), _vp, i64, _vp, _vp],
+        "drl_widenet_dqn_per_train": [D, ctypes.POINTER(DrlDqnHParams), ctypes.POINTER(DrlPerHParams), _vp, _vp,
+                                      ctypes.POINTER(DrlReplay), i64, _vp, _vp],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -1333,6 +1337,56 @@ class PrioritizedDQNLearner(LargeBatchDQNLearner):
         return out.copy_(per.slots)
 
 
+class _PrioritizedTrain:
+    """train(per) and sample_slots(per) of the prioritized conv and wide
+    learners, with PrioritizedDQNLearner's semantics: the C call is
+    `_per_train`'s, the block and everything else the uniform learner's."""
+
+    _per_train = None  # the C call's name
+
+    def train(self, per: "PrioritizedReplay"):
+        """One learner block on the prioritized replay's current contents."""
+        if not isinstance(per, PrioritizedReplay):
+            raise ValueError(f"{type(self).__name__}.train takes a PrioritizedReplay")
+        if per.rb.obs.device != self.block.device:
+            raise ValueError("the replay buffer must be on the learner's device")
+        per.bind(self.hp.batch)
+        _check(self.L, getattr(self.L, self._per_train)(
+            ctypes.byref(self.net.desc), ctypes.byref(self._hp), ctypes.byref(per._hp), _vp(self.block.data_ptr()),
+            _vp(self.net.packed.data_ptr()), ctypes.byref(per.rb._c), per.rb.size, _vp(per.block.data_ptr()),
+            _stream(self.block.device)))
+
+    def sample_slots(self, per: "PrioritizedReplay", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The replay slots (int64 [batch]) the next train(per) draws: a
+        rebuild and a draw at the device step (their weights are left in
+        per.weights); stream-ordered, no sync.  `out`: a copy's destination
+        (default: a new tensor)."""
+        if not isinstance(per, PrioritizedReplay):
+            raise ValueError(f"{type(self).__name__}.sample_slots takes a PrioritizedReplay")
+        if per.rb.obs.device != self.block.device:
+            raise ValueError("the replay buffer must be on the learner's device")
+        per.bind(self.hp.batch)
+        per.rebuild()
+        per.sample(self.hp.sample_seed, self.block.data_ptr() + self.layout.counters_off)
+        if out is None:
+            return per.slots.clone()
+        _on(out, self.block.device, torch.int64, "out")
+        if out.numel() != self.hp.batch or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous int64 [{self.hp.batch}] tensor")
+        return out.copy_(per.slots)
+
+
+class PrioritizedWideDQNLearner(_PrioritizedTrain, WideDQNLearner):
+    """WideDQNLearner on prioritized rows (drl_widenet_dqn_per_train):
+    PrioritizedDQNLearner's launch chain and arithmetic on the wide family's
+    plan (hidden widths up to 256), the agent block WideDQNLearner's, the
+    act's image refreshed by the wide pack kernel.  `train(per)` and
+    `sample_slots(per)` take a PrioritizedReplay; everything else is
+    inherited."""
+
+    _per_train = "drl_widenet_dqn_per_train"
+
+
 def make_learner(net, hp: Optional[DQNHParams] = None, per: bool = False, **kw):
     """A net's learner: for a QNetwork by hp.batch, DQNLearner (one launch,
     batches up to 64) or LargeBatchDQNLearner (a launch chain, batches up to
@@ -1503,3 +1557,31 @@ class LargeBatchConvDQNLearner(ConvDQNLearner):
     plus ceil(batch / 64) x n_params x 4 bytes of partial gradients."""
 
     _abi = "drl_convnet_dqn_large"
+
+
+class PrioritizedConvDQNLearner(_PrioritizedTrain, LargeBatchConvDQNLearner):
+    """LargeBatchConvDQNLearner on prioritized rows
+    (drl_convnet_dqn_per_train), at every batch 1..4096: the same agent
+    block, chain and arithmetic with each drawn row's importance weight on
+    its squared error and on the Q head's delta, and the new priorities
+    (|td error| + eps) ** alpha written to the drawn slots -- stream-ordered,
+    no synchronisation, graph-capturable.  With alpha = 0 and beta = 0 every
+    weight and priority is exactly 1.0 and a step is
+    LargeBatchConvDQNLearner's on the drawn rows bit for bit.  `train(per)`
+    and `sample_slots(per)` take a PrioritizedReplay; block, params,
+    counters, save, restart and check_errors are inherited."""
+
+    _per_train = "drl_convnet_dqn_per_train"
+
+
+def make_per_learner(net, hp: Optional[DQNHParams] = None, **kw):
+    """The prioritized learner of the net's family, at every batch 1..4096:
+    PrioritizedDQNLearner for a QNetwork, PrioritizedWideDQNLearner for a
+    WideQNetwork, PrioritizedConvDQNLearner for a ConvQNetwork.
+    (make_learner(per=True) keeps refusing conv and wide nets.)"""
+    hp = hp or DQNHParams()
+    if isinstance(net, ConvQNetwork):
+        return PrioritizedConvDQNLearner(net, hp, **kw)
+    if isinstance(net, WideQNetwork):
+        return PrioritizedWideDQNLearner(net, hp, **kw)
+    return PrioritizedDQNLearner(net, hp, **kw)

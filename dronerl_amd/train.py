@@ -8,8 +8,8 @@ the drone-0 transitions in the replay ring (drl_step_code_replay:
 buffer.add_many), the learner block (drl_dqn_train: sample + train_step when
 the buffer can sample, the target update, the epsilon decay, step + 1; a
 conv net: drl_convnet_act and drl_convnet_dqn_train; a dense net wider than
-128: drl_widenet_act and drl_widenet_dqn_train; --prioritized_replay: the
-ring wrapped in dqn.PrioritizedReplay and drl_dqn_per_train), and
+128: drl_widenet_act and drl_widenet_dqn_train; prioritized replay: the
+ring wrapped in dqn.PrioritizedReplay and the family's drl_*_dqn_per_train), and
 a reset of every env when step % reset_env_every == 0 (:99-113).
 `evaluate` is eval_jax (:270-319): greedy drone 0 against random drones,
 episodes sharded over ranks with the eval table all-reduced
@@ -69,12 +69,14 @@ def train(params: EnvParams, num_envs: int, num_steps: int, hidden: Sequence[int
     the same learner; env_offset is then ignored.  The returned rate counts
     every rank's envs.
 
-    per (--prioritized_replay): dqn.PrioritizedReplay's keywords (alpha,
-    beta0, beta_steps, eps).  The ring is wrapped in a PrioritizedReplay and
-    the learner is dqn.PrioritizedDQNLearner at every batch; dense nets of
-    widths up to 128 on one GPU only.  The returned `replay` is the wrapper."""
+    per (--prioritized_replay, python -m dronerl_amd.per_train):
+    dqn.PrioritizedReplay's keywords (alpha, beta0, beta_steps, eps).  The
+    ring is wrapped in a PrioritizedReplay and the learner is
+    dqn.make_per_learner's at every batch (PrioritizedDQNLearner, or
+    PrioritizedWideDQNLearner, or PrioritizedConvDQNLearner); one GPU only.
+    The returned `replay` is the wrapper."""
     from .dqn import (ConvQNetwork, DQNHParams, PrioritizedReplay, QNetwork, ReplayBuffer, WideQNetwork, is_wide,
-                      make_learner)
+                      make_learner, make_per_learner)
     from .distributed import shard_envs
     from .env import BatchedDeliveryDrones
     from .global_learner import ShardedReplay
@@ -87,13 +89,8 @@ def train(params: EnvParams, num_envs: int, num_steps: int, hidden: Sequence[int
     wide = network_type == "dense" and is_wide(hidden)
     if wide and world > 1:
         raise ValueError(WIDE_SHARDING_REFUSAL)
-    if per is not None:
-        if network_type == "conv":
-            raise ValueError(PER_CONV_REFUSAL)
-        if wide:
-            raise ValueError(PER_WIDE_REFUSAL)
-        if world > 1:
-            raise ValueError(PER_SHARDING_REFUSAL)
+    if per is not None and world > 1:
+        raise ValueError(PER_SHARDING_REFUSAL)
     shard = shard_envs(num_envs, rank, world) if world > 1 else None
     env = BatchedDeliveryDrones(params, shard.num_envs if shard else num_envs, device=device,
                                 env_offset=shard.env_offset if shard else env_offset)
@@ -108,17 +105,15 @@ def train(params: EnvParams, num_envs: int, num_steps: int, hidden: Sequence[int
         net = ConvQNetwork((W, W, 6), conv_layers if conv_layers is not None else TRAIN_JAX_CONV_LAYERS,
                            tuple(conv_dense_layers), device=dev, generator=torch.Generator().manual_seed(seed),
                            input="code")
-        # (batches up to 64: ConvDQNLearner; up to 4096: LargeBatchConvDQNLearner's chunked gradients)
-        learner = make_learner(net, hp, generator=torch.Generator().manual_seed(seed + 1))
     elif wide:  # (a width above 128: the wide act and the launch-chain learner, dqn.WideDQNLearner)
         net = WideQNetwork(D, tuple(hidden), device=dev, generator=torch.Generator().manual_seed(seed), input="code")
-        learner = make_learner(net, hp, generator=torch.Generator().manual_seed(seed + 1))
     else:
         net = QNetwork(D, tuple(hidden), device=dev, generator=torch.Generator().manual_seed(seed), input="code")
-        # (batches up to 64: DQNLearner's one launch; up to 4096: LargeBatchDQNLearner's launch chain; prioritized
-        # replay: PrioritizedDQNLearner's chain at every batch)
-        learner = make_learner(net, hp, generator=torch.Generator().manual_seed(seed + 1),
-                               **({"per": True} if per is not None else {}))
+    # dense: batches up to 64 DQNLearner's one launch, up to 4096 LargeBatchDQNLearner's launch chain (a wide net:
+    # the chain at every batch); conv: ConvDQNLearner up to 64, LargeBatchConvDQNLearner's chunked gradients above;
+    # prioritized replay: the family's prioritized learner at every batch
+    learner = (make_per_learner if per is not None else make_learner)(
+        net, hp, generator=torch.Generator().manual_seed(seed + 1))
     if shard:
         rb = ShardedReplay(memory_size, D, dev, num_envs, shard.env_offset, shard.num_envs, rank, world,
                            code_radius=r, group=group)
@@ -343,13 +338,17 @@ def main(argv=None) -> dict:
     """`python -m dronerl_amd.train [train_jax.py options]`: train, save
     (train_jax.py:238-244: agent_<n>_steps_jax / _torch.safetensors under
     output/jax_run_<time>), evaluate (:247-256).  Returns the metrics."""
+    return run(parse_args(argv))
+
+
+def run(args) -> dict:
+    """`main` behind the command line: `args` is parse_args' result
+    (dronerl_amd.per_train passes its own, with prioritized replay on)."""
     import json
     import os
     from datetime import datetime
 
-    from .checkpoint import read_checkpoint, to_qnet
     from .distributed import init_from_env
-    args = parse_args(argv)
     rank, world, local = init_from_env() if args.use_sharding else (0, 1, 0)
     if args.use_sharding and args.num_envs % world:
         raise ValueError(f"The number of envs (={args.num_envs}) needs to be divisible by the number of devices "

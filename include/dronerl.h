@@ -939,6 +939,48 @@ int drl_widenet_dqn_sample_rows(const drl_widenet_desc* d, const drl_dqn_hparams
                                 int64_t size, int64_t* d_slots, hipStream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Prioritized replay for the conv and the wide single-agent learners: the
+ * prioritized block is drl_per_layout_query(r->capacity, h->batch)'s, filled
+ * and marked by drl_per_init / drl_per_mark_new as for drl_dqn_per_train; the
+ * agent blocks are the uniform learners' own (there is no new layout), so a
+ * block can be handed from one call to the other.  Both calls make every
+ * check of their uniform learner plus drl_dqn_per_train's (the PER
+ * hyperparameters' ranges, capacity <= DRL_PER_MAX_CAPACITY, d_per 16-byte
+ * aligned) before any device work, allocate nothing, do not synchronise and
+ * are graph-capturable as one linear chain of kernel nodes; no workgroup
+ * waits for another and no float atomic is used (the priorities' maxima are
+ * integer maxima on the positive floats' bits).
+ * ------------------------------------------------------------------------ */
+/* drl_convnet_dqn_large_train on prioritized rows (its arguments, agent block
+ * -- drl_convnet_dqn_large_layout_query / _init -- and arithmetic; batch
+ * 1..4096).  With size >= h->batch, in stream order: rebuild (one or two
+ * launches), sample (seed h->sample_seed, the step of the agent block's
+ * counters), the rows, the dense and the conv layers' chunk partials, the
+ * update, the counters, the priority update, the re-pack.  A row is
+ * drl_convnet_dqn_large_train's at slot slots[b], with weights[b] = w on its
+ * squared error, w * (d * d), and on the Q head's delta,
+ * w * ((d + d) / float(batch)), d = q[a] - td (with w == 1.0 the row is the
+ * uniform learner's bit for bit); the loss is mean(w * d^2) in the uniform
+ * chain's order; |d| goes to the block's absd and the slot's leaf is zeroed.
+ * The priority update is drl_dqn_per_train's: p = (float)pow((double)|d| +
+ * eps, alpha), at most 2^64, the largest over the rows that drew the slot;
+ * pmax = max(pmax, p).  With size < h->batch it is the uniform learner's
+ * no-sample step: the tree, slots, weights and pmax are left alone.
+ * alpha = 0 and beta0 = 0, beta_steps = 0 give weights and priorities of
+ * exactly 1.0. */
+int drl_convnet_dqn_per_train(const drl_convnet_desc* d, const drl_dqn_hparams* h, const drl_per_hparams* ph,
+                              void* d_agent, void* d_packed, const struct drl_replay* r, int64_t size, void* d_per,
+                              hipStream_t stream);
+/* drl_dqn_per_train for a drl_widenet_desc (hidden widths up to
+ * DRL_WIDENET_MAX_WIDTH): the same kernels on the wide family's plan, the
+ * agent block drl_widenet_dqn_layout_query / _init's, then the wide pack
+ * kernel.  At the widths both take, the agent block after a step is
+ * drl_dqn_per_train's byte for byte. */
+int drl_widenet_dqn_per_train(const drl_widenet_desc* d, const drl_dqn_hparams* h, const drl_per_hparams* ph,
+                              void* d_agent, void* d_packed, const struct drl_replay* r, int64_t size, void* d_per,
+                              hipStream_t stream);
+
+/* ------------------------------------------------------------------------
  * A population of dense DQN agents (run_jax_sweep.py, torch_impl/sweep.py:
  * many training runs that differ in their hyperparameters): `members`
  * agents, each the learner block written above drl_dqn_train on its own
