@@ -214,10 +214,14 @@ KERNEL_TESTS = {
     "drl_qnet_act_kernel": "test_dqn.py::test_qnet_greedy_matches_torch_reference",   # bf16
     "drl_qnet_act_f32_kernel": "test_dqn.py::test_qnet_f32_matches_fp32_forward",
     "drl_qnet_act_code_kernel": "test_policy_code.py::test_qnet_act_code_matches_f32_forward",   # other nets
-    "drl_qnet_act_code2_kernel": "test_policy_code.py::test_qnet_act_code_matches_f32_forward",  # kernel="code2"
+    # kernel="code2"; the automatic fallback at E * code_bytes >= 2^31:
+    # test_size_thresholds.py::test_code_act_on_both_sides_of_2gib_of_codes
+    "drl_qnet_act_code2_kernel": "test_policy_code.py::test_qnet_act_code_matches_f32_forward",
     "drl_qnet_act_code4_kernel": "test_policy_code.py::test_qnet_act_code_matches_f32_forward",  # benchmark net
     "drl_replay_add16_kernel": "test_policy_code.py::test_code_replay_buffer_samples_decode_to_obs_buffer",
     "drl_replay_add_kernel": "test_dqn.py::test_replay_add_many_matches_sequential_add",
+    # (also at 294-float rows past the multiply-shift bound:
+    # test_size_thresholds.py::test_replay_add_on_both_sides_of_its_kernel_bound)
     "drl_replay_add_rows_kernel": "test_dqn.py::test_replay_add_two_float_rows",
     "drl_dqn_train_kernel": "test_dqn_learner.py::test_learner_matches_oracle_bit_exact",
     "drl_dqn_init_kernel": "test_dqn_learner.py::test_learner_matches_oracle_bit_exact",
