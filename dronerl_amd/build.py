@@ -51,6 +51,7 @@ DEPS = SOURCES + [os.path.join(CSRC, "dronerl_internal.h"), os.path.join(CSRC, "
                   os.path.join(CSRC, "largelearn", "dronerl_largelearn_layout.h"),
                   os.path.join(CSRC, "largelearn", "dronerl_largelearn_chain.h"),
                   os.path.join(CSRC, "population", "dronerl_population_layout.h"),
+                  os.path.join(CSRC, "population", "dronerl_population_member.h"),
                   os.path.join(CSRC, "league", "dronerl_league_layout.h"),
                   os.path.join(CSRC, "convleague", "dronerl_convleague_layout.h"),
                   os.path.join(CSRC, "convleague", "dronerl_convleague_tile.h"),
@@ -60,7 +61,6 @@ DEPS = SOURCES + [os.path.join(CSRC, "dronerl_internal.h"), os.path.join(CSRC, "
                   os.path.join(CSRC, "per", "dronerl_per_chain.h"),
                   os.path.join(CSRC, "perpop", "dronerl_perpop_layout.h"),
                   os.path.join(CSRC, "convper", "dronerl_convper_layout.h"),
-                  os.path.join(CSRC, "convper", "dronerl_convper_chain.h"),
                   os.path.join(CSRC, "widenet", "dronerl_widenet_layout.h"),
                   os.path.join(CSRC, "evalcode", "dronerl_evalcode_layout.h"),
                   os.path.join(CSRC, "convnet", "dronerl_convnet_layout.h"), os.path.join(REPO, "include", "dronerl.h")]

@@ -24,7 +24,9 @@
 // one chunk (B <= 64) every sum is drl_convnet_dqn_train's own, so the two learners agree bit for bit.  An MFMA
 // sums its K products in an order of its own, so the partials are VALU work.  Every loop bound is the validated
 // plan's (dronerl_convlarge_layout.h).  The kernels' bodies live in dronerl_convlarge_chain.h, which the
-// population's kernels (convpop/dronerl_convpop.hip) run too.
+// population's kernels (convpop/dronerl_convpop.hip) run too.  The prioritized learner (convper/) has a rows kernel
+// of its own (the same body on the drawn rows) and launches this unit's kernels 2.-5. behind it
+// (launch_convlarge_grads_update).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -50,7 +52,7 @@ __global__ void __launch_bounds__(kRowsThreadsMax) drl_convnet_dqn_large_rows_ke
     (void)args;
     const cl::LearnArgs& a = ((const LearnArgs*)__builtin_amdgcn_kernarg_segment_ptr())->a;
     extern __shared__ float4 cg_lds4[];
-    rows_body(a.P, a, a.P.batch, (int)blockIdx.x, reinterpret_cast<float*>(cg_lds4));
+    rows_body(a.P, a, UniformRows{}, a.P.batch, (int)blockIdx.x, reinterpret_cast<float*>(cg_lds4));
 }
 
 // 2. A dense layer's chunk partials: workgroup (tile blockIdx.x, chunk blockIdx.y).
@@ -98,12 +100,13 @@ __global__ void __launch_bounds__(kThreads) drl_convnet_dqn_large_sample_kernel(
     if (b < batch) out[b] = dq_sample(seed, c->step, b, size);
 }
 
-int launch_convlarge_train(const LearnArgs& a, hipStream_t s) {
+// 2.-5. Everything behind the rows: the chunk partials (with a sample), the update, the counters.  The prioritized
+// chain (convper/dronerl_convper.hip) launches these as they are behind its own rows kernel; the caller reads
+// hipGetLastError behind its last launch.
+void launch_convlarge_grads_update(const LearnArgs& a, hipStream_t s) {
     const cl::Plan& P = a.a.P;
     const unsigned chunks = (unsigned)a.t.chunks;
     if (a.a.trained) {
-        hipLaunchKernelGGL(drl_convnet_dqn_large_rows_kernel, dim3((unsigned)P.batch),
-                           dim3((unsigned)a.t.rows_threads), (size_t)P.row_words * 4, s, a);
         hipLaunchKernelGGL(drl_convnet_dqn_large_dense_grad_kernel, dim3((unsigned)a.t.dense_tiles, chunks),
                            dim3(kThreads), 0, s, a);
         hipLaunchKernelGGL(drl_convnet_dqn_large_conv_grad_kernel,
@@ -113,6 +116,14 @@ int launch_convlarge_train(const LearnArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(drl_convnet_dqn_large_update_kernel, dim3((unsigned)((P.n_params + kThreads - 1) / kThreads)),
                        dim3(kThreads), 0, s, a);
     hipLaunchKernelGGL(drl_convnet_dqn_large_counters_kernel, dim3(1), dim3(64), 0, s, a);
+}
+
+int launch_convlarge_train(const LearnArgs& a, hipStream_t s) {
+    const cl::Plan& P = a.a.P;
+    if (a.a.trained)
+        hipLaunchKernelGGL(drl_convnet_dqn_large_rows_kernel, dim3((unsigned)P.batch),
+                           dim3((unsigned)a.t.rows_threads), (size_t)P.row_words * 4, s, a);
+    launch_convlarge_grads_update(a, s);
     return (int)hipGetLastError();
 }
 

@@ -1,7 +1,8 @@
 // dronerl_convlarge_chain.h — the bodies of the conv large-batch learner's launch chain, shared by
 // convlarge/dronerl_convlarge.hip (one agent: drl_convnet_dqn_large_*) and convpop/dronerl_convpop.hip (a
 // population: drl_convpop_*), in the manner of largelearn/dronerl_largelearn_chain.h: both units' kernels run
-// these, so a population member's arithmetic cannot drift from the single agent's.  A body takes the validated
+// these, so a population member's arithmetic cannot drift from the single agent's; the prioritized learner's rows
+// kernel (convper/dronerl_convper.hip) runs rows_body too, on its drawn rows.  A body takes the validated
 // plan (cl::Plan and cg::Tiles: every loop bound), an agent view `a` (any struct with cl::LearnArgs' field names:
 // the parameter sets, the counters, the scratch, the replay ring and the hyperparameters, which
 // dronerl_learn_common.h's functions read), the batch it trains on and its workgroup coordinates.  The single
@@ -28,14 +29,16 @@ namespace {
 typedef float cg_f4 __attribute__((ext_vector_type(4)));
 
 // 1. Row b of the batch (one workgroup, the row's words in LDS): drl_convnet_dqn_rows_kernel's row (the shared
-// per-layer code is cl_forward / cl_backward; the head's delta divides by the full batch).
-template <class V>
-__device__ __forceinline__ void rows_body(const cl::Plan& P, const V& a, int batch, int b, float* row) {
+// per-layer code is cl_forward / cl_backward; the head's delta divides by the full batch).  p: how the row is
+// drawn and weighted (dronerl_learn_common.h: UniformRows, or the prioritized replay's drawn rows, whose weight
+// lies on the squared error and on the head's delta, |d| kept and the slot's leaf zeroed for the priority kernel).
+template <class V, class R>
+__device__ __forceinline__ void rows_body(const cl::Plan& P, const V& a, const R& p, int batch, int b, float* row) {
     const int tid = threadIdx.x, nt = blockDim.x;
     if (b >= batch) return;
     const int L = P.n_layers, A = P.n_actions;
     const int32_t step = a.ctr->step;
-    const int64_t s = dq_sample(a.seed, step, b, a.size);
+    const int64_t s = dq_row_slot(p, a.seed, step, b, a.size);
     for (int i = tid; i < P.row_words; i += nt) row[i] = 0.0f;
     __syncthreads();
     // the target net on next_obs: max_a Q_target
@@ -67,8 +70,10 @@ __device__ __forceinline__ void rows_body(const cl::Plan& P, const V& a, int bat
         const float td = rew + (a.gamma * mx) * notdone;
         const bool ok = act >= 0 && act < A;  // (an action outside [0, A) adds nothing)
         const float d = (ok ? dq[act] : td) - td;
-        for (int j = 0; j < A; ++j) dq[j] = (ok && j == act) ? (d + d) / (float)batch : 0.0f;
-        a.scratch[P.sq_off + b] = d * d;
+        const auto w = dq_row_weight(p, b);
+        for (int j = 0; j < A; ++j) dq[j] = (ok && j == act) ? dq_weighted(w, (d + d) / (float)batch) : 0.0f;
+        a.scratch[P.sq_off + b] = dq_weighted(w, d * d);
+        dq_row_keep(p, b, s, d);
     }
     __syncthreads();
     for (int l = L - 1; l >= 1; --l) {

@@ -134,6 +134,10 @@ struct LearnArgs {
 
 // (hipError_t values) one learner step's launches, in stream order
 int launch_convlarge_train(const LearnArgs& a, hipStream_t s);
+// ... and that chain behind its rows kernel (the chunk partials with a sample, the update, the counters), which
+// the prioritized chain (convper/) launches as it is.  (No error is read: the caller reads hipGetLastError behind
+// its last launch.)
+void launch_convlarge_grads_update(const LearnArgs& a, hipStream_t s);
 int launch_convlarge_sample(const void* counters, uint64_t seed, int batch, int64_t size, int64_t* out, hipStream_t s);
 
 }  // namespace cg

@@ -51,13 +51,7 @@ int drl_convnet_dqn_per_train(const drl_convnet_desc* d, const drl_dqn_hparams* 
         return fail(msg);
     drl::fill_learn_args(a, P.pub, P.code_w, h, d_agent, r, size);
     const drl::per::TreeArgs t = drl::per::tree_args(T, d_per);
-    full.d.slots = t.slots;
-    full.d.weights = t.weights;
-    full.d.absd = t.absd;
-    full.d.leaves = t.tree + t.P;
-    full.d.pmax = t.pmax;
-    full.d.alpha = ph->alpha;
-    full.d.per_eps = ph->eps;
+    full.d = drl::per::drawn_of(t, ph->alpha, ph->eps);
     const drl::per::SampleArgs sa = {h->sample_seed, size, ph->beta0, ph->beta_steps};
     // the act's image of the new online set, as drl_convnet_dqn_large_train refreshes it: the pack kernel on the
     // online set behind the counters kernel's store of the status vector's zeros (kernel nodes only)

@@ -15,21 +15,11 @@ namespace cper {
 
 static_assert(per::kMaxBatch == cg::kMaxBatch, "one prioritized block serves both learners' batches");
 
-// One step's drawn rows and the tree's leaves, as the rows and the priority kernels see them (the names are
-// per::LearnArgs': per::priority_body reads this view as it reads the dense learner's arguments).
-struct Drawn {
-    const int64_t* slots;  // [batch]: the drawn slots
-    const float* weights;  // [batch]: their importance weights, w / wmax
-    float* absd;           // [batch]: |q - td| of the rows
-    float* leaves;         // tree + P: slot s's leaf is leaves[s]
-    float* pmax;
-    double alpha, per_eps;
-};
-
 // the conv large-batch chain's arguments and the step's drawn rows
 struct LearnArgs {
-    cg::LearnArgs c;  // (c.a is the agent view the chain's bodies take, c.t the chain's tiles)
-    Drawn d;
+    cg::LearnArgs c;  // (c.a is the agent view the chain's bodies take, c.t the chain's tiles; the uniform
+                      // kernels of the chain are launched with c)
+    per::Drawn d;
 };
 static_assert(sizeof(LearnArgs) <= 4096, "the arguments are read in place from the kernarg segment");
 

@@ -28,6 +28,7 @@
 #include "../dronerl_learn_common.h"
 #include "../convlearn/dronerl_convlearn_rows.h"
 #include "../convlarge/dronerl_convlarge_chain.h"
+#include "../population/dronerl_population_member.h"  // pop::hparams_into: the record's copy into a view
 #include "dronerl_convpop_layout.h"
 
 // every product and sum rounds on its own (no FMA contraction), as in the other learners
@@ -86,21 +87,7 @@ __device__ __forceinline__ Member member_of(const PopArgs& a, int m) {
     v.r_done = a.r_done + r0;
     v.size = a.size;
     v.seed = h.seed;
-    v.gamma = h.gamma;
-    v.b1 = h.b1;
-    v.b2 = h.b2;
-    v.c1 = h.c1;
-    v.c2 = h.c2;
-    v.adam_eps = h.adam_eps;
-    v.neg_lr = h.neg_lr;
-    v.tau = h.tau;
-    v.one_minus_tau = h.one_minus_tau;
-    v.eps_decay = h.eps_decay;
-    v.eps_end = h.eps_end;
-    v.b1d = h.b1d;
-    v.b2d = h.b2d;
-    v.target_every = h.target_every;
-    v.eps_every = h.eps_every;
+    pop::hparams_into(h, v);
     return v;
 }
 
@@ -195,7 +182,7 @@ __global__ void __launch_bounds__(cg::kRowsThreadsMax) drl_convpop_rows_kernel(P
     extern __shared__ float4 cp_lds4[];
     const Member v = member_of(a, blockIdx.y);
     if (a.size < v.batch) return;  // (uniform over the workgroup, as the row's own bound in the body)
-    cg::rows_body(a.P, v, v.batch, (int)blockIdx.x, reinterpret_cast<float*>(cp_lds4));
+    cg::rows_body(a.P, v, UniformRows{}, v.batch, (int)blockIdx.x, reinterpret_cast<float*>(cp_lds4));
 }
 
 // 2. dense partials: grid (dense tiles, chunks of max_batch, members)

@@ -1,7 +1,8 @@
 // dronerl_learn_common.h — device code shared by the DQN learners (dronerl_learn.hip, the dense nets' single
 // launch; convlearn/dronerl_convlearn.hip, the conv nets' launch chain), in the manner of dronerl_act_common.h:
-// the replay row draw, a row's input decode, optax's Adam and incremental_update, and the counters at the end of
-// a step.  Both learners include it, so they cannot drift apart on the sample hash, the Adam formula or the
+// the replay row draw, the launch chains' policy of how a row is drawn and weighted (uniform or prioritized), a
+// row's input decode, optax's Adam and incremental_update, and the counters at the end of a step.  Every learner
+// includes it, so they cannot drift apart on the sample hash, the TD rule's weighting, the Adam formula or the
 // epsilon schedule.  The functions take the learner's own argument block (any struct with the fields they
 // name): the dense learner's LearnArgs, the conv learner's cl::LearnArgs.
 #pragma once
@@ -21,6 +22,51 @@ namespace drl {
 __device__ __forceinline__ int64_t dq_sample(uint64_t seed, int32_t step, int b, int64_t size) {
     const uint64_t h = splitmix64(seed ^ splitmix64(((uint64_t)(uint32_t)step << 16) | (uint64_t)b));
     return (int64_t)(((h >> 32) * (uint64_t)size) >> 32);
+}
+
+// How a launch chain's row b is drawn and weighted: the one thing in which a uniform chain and a prioritized one
+// differ.  The chains' rows and TD bodies take the policy as `p` and are compiled once for each:
+//   UniformRows     the slot is dq_sample's; no weight; nothing is kept.
+//   a drawn view    (any struct with per::Drawn's fields, per/dronerl_per_layout.h) the slot and the importance
+//                   weight are the sampler's; the weight lies on the row's squared error and on the Q head's
+//                   delta; |d| is kept for the priority kernel and the slot's leaf zeroed, so that the integer
+//                   max there starts from 0.0 (a slot drawn by several rows is zeroed by each: the same store).
+// The choice is the overload's, at compile time: the uniform kernels hold no weight load and no multiply.
+struct UniformRows {};
+
+// Row b's slot.  The arguments are dq_sample's, which a drawn row leaves unread: each body names them in the order
+// in which it has always read them.
+__device__ __forceinline__ int64_t dq_row_slot(const UniformRows&, uint64_t seed, int32_t step, int b, int64_t size) {
+    return dq_sample(seed, step, b, size);
+}
+template <class Drawn>
+__device__ __forceinline__ int64_t dq_row_slot(const Drawn& p, uint64_t, int32_t, int b, int64_t) {
+    return p.slots[b];
+}
+
+// Row b's importance weight, read once, and a term x of the row's loss under it: the uniform case has no weight
+// to read and x stays as it is (no multiply by 1.0)
+struct Unweighted {};
+__device__ __forceinline__ Unweighted dq_row_weight(const UniformRows&, int) { return Unweighted{}; }
+template <class Drawn>
+__device__ __forceinline__ float dq_row_weight(const Drawn& p, int b) {
+    return p.weights[b];
+}
+__device__ __forceinline__ float dq_weighted(Unweighted, float x) { return x; }
+__device__ __forceinline__ float dq_weighted(float w, float x) { return w * x; }
+
+// What is kept of row b (replay slot s) once its TD error d is known.  A body that does not hold the slot leaves
+// it out: a drawn row's is read again, a uniform row's never computed.
+__device__ __forceinline__ void dq_row_keep(const UniformRows&, int, int64_t, float) {}
+__device__ __forceinline__ void dq_row_keep(const UniformRows&, int, float) {}
+template <class Drawn>
+__device__ __forceinline__ void dq_row_keep(const Drawn& p, int b, int64_t s, float d) {
+    p.absd[b] = __builtin_fabsf(d);
+    p.leaves[s] = 0.0f;
+}
+template <class Drawn>
+__device__ __forceinline__ void dq_row_keep(const Drawn& p, int b, float d) {
+    dq_row_keep(p, b, p.slots[b], d);
 }
 
 // Input k of replay row s: a policy-code row is decoded with the channel rules

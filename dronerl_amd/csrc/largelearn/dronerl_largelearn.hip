@@ -23,7 +23,9 @@
 // a workgroup takes 64 rows, one per lane, by 16 outputs, four per wave; the rows' operand goes through LDS in
 // 128-column chunks (one 16-B read feeds the four partial sums of four outputs) and the weights are read at
 // wave-uniform addresses.  Every loop bound is the validated plan's (dronerl_largelearn_layout.h).  The kernels'
-// bodies live in dronerl_largelearn_chain.h, which the population's learner (population/) includes too.
+// bodies live in dronerl_largelearn_chain.h, which the population's learner (population/) includes too.  The
+// prioritized learner (per/dronerl_per.hip) has rows and TD kernels of its own (the same bodies on the drawn
+// rows) and launches this unit's forward, backward, update, blend and counters kernels through launch_large_*.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -42,7 +44,7 @@ namespace ll {
 __global__ void __launch_bounds__(kThreads) drl_dqn_large_rows_kernel(LearnArgs args) {
     (void)args;
     const LearnArgs& a = *(const LearnArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-    rows_body(a.P, a, a.P.batch, (int64_t)blockIdx.x * kThreads + threadIdx.x);
+    rows_body(a.P, a, UniformRows{}, a.P.batch, (int64_t)blockIdx.x * kThreads + threadIdx.x);
 }
 
 // 2. Layer l of both nets (blockIdx.y: 0 the online net on obs, 1 the target net on next_obs; forward_body).
@@ -57,7 +59,7 @@ __global__ void __launch_bounds__(kTileThreads) drl_dqn_large_forward_kernel(Lea
 __global__ void __launch_bounds__(kThreads) drl_dqn_large_td_kernel(LearnArgs args) {
     (void)args;
     const LearnArgs& a = *(const LearnArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-    td_body(a.P, a, a.P.batch, (int)(blockIdx.x * kThreads + threadIdx.x));
+    td_body(a.P, a, UniformRows{}, a.P.batch, (int)(blockIdx.x * kThreads + threadIdx.x));
 }
 
 // 4. Layer l - 1's deltas from layer l's (l >= 1; backward_body).
@@ -106,33 +108,56 @@ __global__ void __launch_bounds__(kThreads) drl_dqn_large_sample_kernel(const Dq
     if (b < batch) out[b] = dq_sample(seed, c->step, b, size);
 }
 
+// ---- the chain's segments: the launches a prioritized chain (per/dronerl_per.hip) takes over as they are.  The
+// grid arithmetic lives here alone; the caller reads hipGetLastError behind its last launch.
+// 2. every layer's forward
+void launch_large_forward(const LearnArgs& a, hipStream_t s) {
+    const Plan& P = a.P;
+    for (int l = 0; l < P.n_layers; ++l)
+        hipLaunchKernelGGL(drl_dqn_large_forward_kernel, dim3((unsigned)row_tiles(P), 2, (unsigned)unit_tiles(P.out[l])),
+                           dim3(kTileThreads), 0, s, a, l);
+}
+
+// 4.-5. the backward pass of every layer >= 1, then the update
+void launch_large_backward_update(const LearnArgs& a, hipStream_t s) {
+    const Plan& P = a.P;
+    const int L = P.n_layers;
+    for (int l = L - 1; l >= 1; --l)
+        hipLaunchKernelGGL(drl_dqn_large_backward_kernel, dim3((unsigned)row_tiles(P), 1, (unsigned)unit_tiles(P.in[l])),
+                           dim3(kTileThreads), 0, s, a, l);
+    int kt = 0, jt = 0;  // (the widest layer's tiles; a workgroup outside its layer's returns at once)
+    for (int l = 0; l < L; ++l) {
+        kt = update_col_tiles(P, l) > kt ? update_col_tiles(P, l) : kt;
+        jt = update_unit_tiles(P, l) > jt ? update_unit_tiles(P, l) : jt;
+    }
+    hipLaunchKernelGGL(drl_dqn_large_update_kernel, dim3((unsigned)kt, (unsigned)jt, (unsigned)L),
+                       dim3(kUpdateThreads), 0, s, a);
+}
+
+// a step without a sample: the blend
+void launch_large_blend(const LearnArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(drl_dqn_large_blend_kernel, dim3((unsigned)((a.P.n_params + kThreads - 1) / kThreads)),
+                       dim3(kThreads), 0, s, a);
+}
+
+// 6. the counters
+void launch_large_counters(const LearnArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(drl_dqn_large_counters_kernel, dim3(1), dim3(kThreads), 0, s, a);
+}
+
 int launch_large_train(const LearnArgs& a, hipStream_t s) {
     const Plan& P = a.P;
     const dim3 eb(kThreads);
     if (a.trained) {
-        const int L = P.n_layers;
-        const unsigned rt = (unsigned)row_tiles(P);
         const int64_t elems = 2 * (int64_t)P.batch * P.in4;
         hipLaunchKernelGGL(drl_dqn_large_rows_kernel, dim3((unsigned)((elems + kThreads - 1) / kThreads)), eb, 0, s, a);
-        for (int l = 0; l < L; ++l)
-            hipLaunchKernelGGL(drl_dqn_large_forward_kernel, dim3(rt, 2, (unsigned)unit_tiles(P.out[l])),
-                               dim3(kTileThreads), 0, s, a, l);
+        launch_large_forward(a, s);
         hipLaunchKernelGGL(drl_dqn_large_td_kernel, dim3((unsigned)((P.batch + kThreads - 1) / kThreads)), eb, 0, s, a);
-        for (int l = L - 1; l >= 1; --l)
-            hipLaunchKernelGGL(drl_dqn_large_backward_kernel, dim3(rt, 1, (unsigned)unit_tiles(P.in[l])),
-                               dim3(kTileThreads), 0, s, a, l);
-        int kt = 0, jt = 0;  // (the widest layer's tiles; a workgroup outside its layer's returns at once)
-        for (int l = 0; l < L; ++l) {
-            kt = update_col_tiles(P, l) > kt ? update_col_tiles(P, l) : kt;
-            jt = update_unit_tiles(P, l) > jt ? update_unit_tiles(P, l) : jt;
-        }
-        hipLaunchKernelGGL(drl_dqn_large_update_kernel, dim3((unsigned)kt, (unsigned)jt, (unsigned)L),
-                           dim3(kUpdateThreads), 0, s, a);
+        launch_large_backward_update(a, s);
     } else {
-        hipLaunchKernelGGL(drl_dqn_large_blend_kernel, dim3((unsigned)((P.n_params + kThreads - 1) / kThreads)), eb, 0,
-                           s, a);
+        launch_large_blend(a, s);
     }
-    hipLaunchKernelGGL(drl_dqn_large_counters_kernel, dim3(1), eb, 0, s, a);
+    launch_large_counters(a, s);
     return (int)hipGetLastError();
 }
 

@@ -1,7 +1,9 @@
 // dronerl_largelearn_chain.h — the bodies of the large-batch learner's launch chain (device only), shared by the
 // single-agent kernels (dronerl_largelearn.hip) and the population's (population/dronerl_population.hip), in the
 // manner of convlearn/dronerl_convlearn_rows.h: both include it, so one agent's step and a population member's
-// cannot drift apart on the arithmetic order.  A body takes the validated plan `P` (scratch offsets, strides and
+// cannot drift apart on the arithmetic order.  The prioritized chains (per/, perpop/) run these bodies too: their
+// rows and TD kernels pass the drawn rows as the rows' policy, every other step of theirs is a launch of the
+// uniform kernels.  A body takes the validated plan `P` (scratch offsets, strides and
 // layer sizes: sized for the block's batch), the agent's view `a` (any struct with ll::LearnArgs' pointer, replay
 // and hyperparameter fields: LearnArgs itself, or a population member's view), the batch `B` the step trains on
 // (P.batch for one agent; a member's own batch <= P.batch in a population) and the workgroup's coordinates, which
@@ -88,15 +90,16 @@ __device__ __forceinline__ void ll_tile(const float* __restrict__ A, int lda, in
 }
 
 // 1. The rows.  Element e of 2 nets x B x in4: input k of row b's obs (n = 0) or next_obs (n = 1), 0.0 in the
-// pad columns; the k = 0 element of n = 0 also gathers the row's action, reward and done.
-template <class A>
-__device__ __forceinline__ void rows_body(const Plan& P, const A& a, int B, int64_t e) {
+// pad columns; the k = 0 element of n = 0 also gathers the row's action, reward and done.  p: how the row is
+// drawn (dronerl_learn_common.h: UniformRows, or the prioritized replay's drawn rows).
+template <class A, class R>
+__device__ __forceinline__ void rows_body(const Plan& P, const A& a, const R& p, int B, int64_t e) {
     const int64_t per = (int64_t)B * P.in4;
     if (e >= 2 * per) return;
     const int n = e >= per ? 1 : 0;
     const int64_t r = e - n * per;
     const int b = (int)(r / P.in4), k = (int)(r - (int64_t)b * P.in4);
-    const int64_t s = dq_sample(a.seed, a.ctr->step, b, a.size);
+    const int64_t s = dq_row_slot(p, a.seed, a.ctr->step, b, a.size);
     a.scratch[x_word(P, n, b, k)] = k < P.in[0] ? dq_input(a, n ? a.r_next : a.r_obs, s, k) : 0.0f;
     if (n == 0 && k == 0) {
         reinterpret_cast<int32_t*>(a.scratch)[P.act_off + b] = a.r_act[s];
@@ -133,10 +136,11 @@ __device__ __forceinline__ void forward_body(const Plan& P, const A& a, int B, i
 }
 
 // 3. The TD error of row b (dqn.py:147-183): td = r + gamma * max_a Q_target * (1 - done), d = q[a] - td, the
-// row's squared error and the Q head's deltas d loss / d q[b][a_b] = 2 d / B.  An action outside [0, A) adds
-// nothing (d = 0, no delta), as in drl_dqn_train.
-template <class A>
-__device__ __forceinline__ void td_body(const Plan& P, const A& a, int B, int b) {
+// row's squared error and the Q head's deltas d loss / d q[b][a_b] = 2 d / B, both under the row's importance
+// weight when p is a prioritized draw (dq_row_weight), which also keeps |d| and zeroes the slot's leaf
+// (dq_row_keep).  An action outside [0, A) adds nothing (d = 0, no delta), as in drl_dqn_train.
+template <class A, class R>
+__device__ __forceinline__ void td_body(const Plan& P, const A& a, const R& p, int B, int b) {
     if (b >= B) return;
     const int L = P.n_layers, NA = P.out[L - 1];
     const float* q = a.scratch + h_word(P, 0, L - 1, b, 0);
@@ -152,10 +156,12 @@ __device__ __forceinline__ void td_body(const Plan& P, const A& a, int B, int b)
     for (int j = 0; j < NA; ++j)
         if (ok && j == act) qa = q[j];
     const float d = qa - td;
-    a.scratch[P.sq_off + b] = d * d;
+    const auto w = dq_row_weight(p, b);
+    a.scratch[P.sq_off + b] = dq_weighted(w, d * d);
     float* dq = a.scratch + d_word(P, L - 1, b, 0);
-    const float g = (d + d) / (float)B;
+    const float g = dq_weighted(w, (d + d) / (float)B);
     for (int j = 0; j < P.ld[L - 1]; ++j) dq[j] = (ok && j == act) ? g : 0.0f;
+    dq_row_keep(p, b, d);
 }
 
 // 4. Layer l - 1's deltas from layer l's (l >= 1): relu'(z_{l-1}) * sum over j of D_l[b][j] W_l[j][i], the

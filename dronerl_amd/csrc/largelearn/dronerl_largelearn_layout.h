@@ -164,6 +164,13 @@ struct LearnArgs {
 
 // (hipError_t values) one learner step's launches in stream order, without the pack; the slots of the next step
 int launch_large_train(const LearnArgs& a, hipStream_t s);
+// ... and the segments of that chain which the prioritized chain (per/) launches as they are: every layer's
+// forward; the backward pass and the update; the no-sample step's blend; the counters.  (No error is read: the
+// caller reads hipGetLastError behind its last launch.)
+void launch_large_forward(const LearnArgs& a, hipStream_t s);
+void launch_large_backward_update(const LearnArgs& a, hipStream_t s);
+void launch_large_blend(const LearnArgs& a, hipStream_t s);
+void launch_large_counters(const LearnArgs& a, hipStream_t s);
 int launch_large_sample(const void* counters, uint64_t seed, int batch, int64_t size, int64_t* out, hipStream_t s);
 
 }  // namespace ll

@@ -9,16 +9,18 @@
 //   drl_per_sample_kernel    one row per stratum: a counter hash places the row's mass in its stratum, the descent
 //                            reads the tree's top from LDS and the rest from L2; the importance weights and their
 //                            maximum (an integer max on the positive floats' bits, in LDS) in the same workgroup;
-//   drl_dqn_per_rows / forward / td / priority / backward / update / blend / counters _kernel
-//                            the large-batch learner's chain (largelearn/dronerl_largelearn_chain.h: the same
-//                            bodies the uniform learner's kernels run) on the drawn rows.  Only the rows and the TD
-//                            bodies are new (per_rows_body, per_td_body): the drawn slot instead of dq_sample, the
-//                            row's weight on its squared error and on the Q head's delta, |d| kept and the slot's
-//                            leaf zeroed; the priority kernel then raises each drawn leaf to its rows' largest new
-//                            priority with an integer max on the float's bits (positive floats order as unsigned
-//                            integers), and pmax the same way.
-// The rebuild's, the sampler's, the rows', the TD's and the priority kernel's bodies live in dronerl_per_chain.h,
-// which the prioritized population (perpop/dronerl_perpop.hip) includes too.
+//   drl_dqn_per_rows / td / priority _kernel
+//                            what the large-batch learner's chain (largelearn/) does differently on drawn rows.
+//                            The rows and the TD kernels run the uniform chain's bodies (ll::rows_body,
+//                            ll::td_body) with the drawn rows as the rows' policy (dronerl_learn_common.h): the
+//                            drawn slot instead of dq_sample, the row's weight on its squared error and on the Q
+//                            head's delta, |d| kept and the slot's leaf zeroed; the priority kernel then raises
+//                            each drawn leaf to its rows' largest new priority with an integer max on the float's
+//                            bits (positive floats order as unsigned integers), and pmax the same way.  The
+//                            forward, backward, update, blend and counters launches of a step are the uniform
+//                            learner's own kernels (ll::launch_large_*), on the base of the arguments.
+// The rebuild's, the sampler's and the priority kernel's bodies live in dronerl_per_chain.h, which the prioritized
+// population (perpop/dronerl_perpop.hip) includes too.
 // No workgroup waits for another and no float atomic is used: nothing depends on scheduling.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -69,65 +71,28 @@ __global__ void __launch_bounds__(kSampleThreads) drl_per_sample_kernel(TreeArgs
     sample_body(t, s, ctr->step, top, &wmax_bits);
 }
 
-// ---- the learner (per_rows_body, per_td_body, priority_body: dronerl_per_chain.h) ------------------------------
+// ---- the learner: the chain's rows and TD bodies on the drawn rows (a.d), and the priorities ------------------
+// 1. The rows (ll::rows_body): the drawn slot in place of dq_sample.
 __global__ void __launch_bounds__(kThreads) drl_dqn_per_rows_kernel(LearnArgs args) {
     (void)args;
     const LearnArgs& a = *(const LearnArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-    per_rows_body(a.P, a, a.P.batch, (int64_t)blockIdx.x * kThreads + threadIdx.x);
+    ll::rows_body(a.P, a, a.d, a.P.batch, (int64_t)blockIdx.x * kThreads + threadIdx.x);
 }
 
-__global__ void __launch_bounds__(ll::kTileThreads) drl_dqn_per_forward_kernel(LearnArgs args, int l) {
-    (void)args;
-    const LearnArgs& a = *(const LearnArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-    __shared__ __attribute__((aligned(16))) float Xs[ll::kTileRows * ll::kChunkStride];
-    ll::forward_body(a.P, a, a.P.batch, l, (int)blockIdx.y, (int)blockIdx.x, (int)blockIdx.z, Xs);
-}
-
+// 3. The TD error (ll::td_body): the row's weight on its squared error and on the Q head's delta, |d| kept, the
+// slot's leaf zeroed.
 __global__ void __launch_bounds__(kThreads) drl_dqn_per_td_kernel(LearnArgs args) {
     (void)args;
     const LearnArgs& a = *(const LearnArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-    per_td_body(a.P, a, a.P.batch, (int)(blockIdx.x * kThreads + threadIdx.x));
+    ll::td_body(a.P, a, a.d, a.P.batch, (int)(blockIdx.x * kThreads + threadIdx.x));
 }
 
-// 6. The priorities (priority_body): each drawn leaf raised to its rows' largest new priority, and pmax.
+// The priorities (priority_body): each drawn leaf raised to its rows' largest new priority, and pmax.
 __global__ void __launch_bounds__(kThreads) drl_dqn_per_priority_kernel(LearnArgs args) {
     (void)args;
     const LearnArgs& a = *(const LearnArgs*)__builtin_amdgcn_kernarg_segment_ptr();
     __shared__ uint32_t wg_max;
-    priority_body(a, a.P.batch, (int)(blockIdx.x * kThreads + threadIdx.x), &wg_max);
-}
-
-__global__ void __launch_bounds__(ll::kTileThreads) drl_dqn_per_backward_kernel(LearnArgs args, int l) {
-    (void)args;
-    const LearnArgs& a = *(const LearnArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-    __shared__ __attribute__((aligned(16))) float Xs[ll::kTileRows * ll::kChunkStride];
-    ll::backward_body(a.P, a, a.P.batch, l, (int)blockIdx.x, (int)blockIdx.z, Xs);
-}
-
-__global__ void __launch_bounds__(ll::kUpdateThreads) drl_dqn_per_update_kernel(LearnArgs args) {
-    (void)args;
-    const LearnArgs& a = *(const LearnArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-    __shared__ __attribute__((aligned(16))) float Xs[ll::kUpdateChunk * ll::kUpdateCols];
-    __shared__ __attribute__((aligned(16))) float Ds[ll::kUpdateChunk * ll::kUpdateUnits];
-    ll::update_body(a.P, a, a.P.batch, (int)blockIdx.z, (int)blockIdx.x, (int)blockIdx.y, Xs, Ds);
-}
-
-// A step without a sample: the target blend when due, over the whole set.
-__global__ void __launch_bounds__(kThreads) drl_dqn_per_blend_kernel(LearnArgs args) {
-    (void)args;
-    const LearnArgs& a = *(const LearnArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (i >= a.P.n_params) return;
-    ll::blend_body(a, i);
-}
-
-// The counters (one workgroup); the act image's status vector cleared for the pack launch that follows.
-__global__ void __launch_bounds__(kThreads) drl_dqn_per_counters_kernel(LearnArgs args) {
-    (void)args;
-    const LearnArgs& a = *(const LearnArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-    __shared__ float sq[ll::kMaxBatch];
-    if (threadIdx.x < 4) a.pack_status[threadIdx.x] = 0u;
-    ll::counters_body(a.P, a, a.P.batch, a.trained, sq);
+    priority_body(a.d, a.P.batch, (int)(blockIdx.x * kThreads + threadIdx.x), &wg_max);
 }
 
 // ---- launches ------------------------------------------------------------------------------------------------
@@ -163,36 +128,26 @@ int launch_sample(const TreeArgs& t, const SampleArgs& a, const void* counters, 
     return (int)hipGetLastError();
 }
 
+// The uniform chain (ll::launch_large_train) on the drawn rows: rebuild and sample in front, this unit's rows and
+// TD kernels in place of the uniform ones, the priorities behind the TD; every other launch is the uniform
+// chain's own kernel with the uniform arguments (a's base).
 int launch_per_train(const LearnArgs& a, const TreeArgs& t, const SampleArgs& sa, hipStream_t s) {
     const ll::Plan& P = a.P;
     const dim3 eb(kThreads);
     if (a.trained) {
         if (const int e = launch_rebuild(t, s)) return e;
         if (const int e = launch_sample(t, sa, a.ctr, s)) return e;
-        const int L = P.n_layers;
-        const unsigned rt = (unsigned)ll::row_tiles(P), bt = (unsigned)((P.batch + kThreads - 1) / kThreads);
+        const unsigned bt = (unsigned)((P.batch + kThreads - 1) / kThreads);
         const int64_t elems = 2 * (int64_t)P.batch * P.in4;
         hipLaunchKernelGGL(drl_dqn_per_rows_kernel, dim3((unsigned)((elems + kThreads - 1) / kThreads)), eb, 0, s, a);
-        for (int l = 0; l < L; ++l)
-            hipLaunchKernelGGL(drl_dqn_per_forward_kernel, dim3(rt, 2, (unsigned)ll::unit_tiles(P.out[l])),
-                               dim3(ll::kTileThreads), 0, s, a, l);
+        ll::launch_large_forward(a, s);
         hipLaunchKernelGGL(drl_dqn_per_td_kernel, dim3(bt), eb, 0, s, a);
         hipLaunchKernelGGL(drl_dqn_per_priority_kernel, dim3(bt), eb, 0, s, a);
-        for (int l = L - 1; l >= 1; --l)
-            hipLaunchKernelGGL(drl_dqn_per_backward_kernel, dim3(rt, 1, (unsigned)ll::unit_tiles(P.in[l])),
-                               dim3(ll::kTileThreads), 0, s, a, l);
-        int kt = 0, jt = 0;  // (the widest layer's tiles; a workgroup outside its layer's returns at once)
-        for (int l = 0; l < L; ++l) {
-            kt = ll::update_col_tiles(P, l) > kt ? ll::update_col_tiles(P, l) : kt;
-            jt = ll::update_unit_tiles(P, l) > jt ? ll::update_unit_tiles(P, l) : jt;
-        }
-        hipLaunchKernelGGL(drl_dqn_per_update_kernel, dim3((unsigned)kt, (unsigned)jt, (unsigned)L),
-                           dim3(ll::kUpdateThreads), 0, s, a);
+        ll::launch_large_backward_update(a, s);
     } else {
-        hipLaunchKernelGGL(drl_dqn_per_blend_kernel, dim3((unsigned)((P.n_params + kThreads - 1) / kThreads)), eb, 0, s,
-                           a);
+        ll::launch_large_blend(a, s);
     }
-    hipLaunchKernelGGL(drl_dqn_per_counters_kernel, dim3(1), eb, 0, s, a);
+    ll::launch_large_counters(a, s);
     return (int)hipGetLastError();
 }
 

@@ -56,13 +56,7 @@ int per_learn_args(drl::per::LearnArgs& a, int in_features, const drl_dqn_hparam
         return fail(msg);
     drl::fill_learn_args(a, P.pub, P.code_w, h, d_agent, r, size);
     *t = drl::per::tree_args(T, d_per);
-    a.slots = t->slots;
-    a.weights = t->weights;
-    a.absd = t->absd;
-    a.leaves = t->tree + t->P;
-    a.pmax = t->pmax;
-    a.alpha = ph->alpha;
-    a.per_eps = ph->eps;
+    a.d = drl::per::drawn_of(*t, ph->alpha, ph->eps);
     *sa = drl::per::SampleArgs{h->sample_seed, size, ph->beta0, ph->beta_steps};
     return 0;
 }

@@ -1,10 +1,10 @@
 // dronerl_per_chain.h — the bodies of the prioritized replay's kernels (device only), shared by the single-agent
-// kernels (dronerl_per.hip) and the prioritized population's (perpop/dronerl_perpop.hip), in the manner of
-// largelearn/dronerl_largelearn_chain.h: both include it, so one agent's tree, draw, weights and priorities and
-// a population member's cannot drift apart on the arithmetic.  A body takes the tree's view (per::TreeArgs: one
-// agent's block, or a member's block with the member's own batch), the learner's view `a` (any struct with
-// ll::LearnArgs' fields and per::LearnArgs' slots, weights, absd, leaves, pmax, alpha, per_eps) and the
-// workgroup's coordinates, which the calling kernel reads from its grid.
+// kernels (dronerl_per.hip), the prioritized population's (perpop/dronerl_perpop.hip) and, for the priorities, the
+// conv learner's (convper/dronerl_convper.hip), in the manner of largelearn/dronerl_largelearn_chain.h: all
+// include it, so one agent's tree, draw, weights and priorities and a population member's cannot drift apart on
+// the arithmetic.  A body takes the tree's view (per::TreeArgs: one agent's block, or a member's block with the
+// member's own batch) or the step's drawn rows (per::Drawn) and the workgroup's coordinates, which the calling
+// kernel reads from its grid.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -112,57 +112,13 @@ __device__ __forceinline__ void sample_body(const TreeArgs& t, const SampleArgs&
 }
 
 // ---- the learner -----------------------------------------------------------------------------------------------
-// 1. The rows: ll::rows_body with the drawn slot in place of dq_sample.
-template <class A>
-__device__ __forceinline__ void per_rows_body(const ll::Plan& P, const A& a, int B, int64_t e) {
-    const int64_t per = (int64_t)B * P.in4;
-    if (e >= 2 * per) return;
-    const int n = e >= per ? 1 : 0;
-    const int64_t r = e - n * per;
-    const int b = (int)(r / P.in4), k = (int)(r - (int64_t)b * P.in4);
-    const int64_t s = a.slots[b];
-    a.scratch[ll::x_word(P, n, b, k)] = k < P.in[0] ? dq_input(a, n ? a.r_next : a.r_obs, s, k) : 0.0f;
-    if (n == 0 && k == 0) {
-        reinterpret_cast<int32_t*>(a.scratch)[P.act_off + b] = a.r_act[s];
-        a.scratch[P.rew_off + b] = a.r_rew[s];
-        a.scratch[P.done_off + b] = a.r_done[s] ? 1.0f : 0.0f;
-    }
-}
-
-// 3. The TD error of row b: ll::td_body with the row's importance weight w on its squared error and on the Q
-// head's delta; |d| is kept for the priority kernel and the slot's leaf zeroed, so that the integer max there
-// starts from 0.0 (a slot drawn by several rows is zeroed by each of them: the same store).
-template <class A>
-__device__ __forceinline__ void per_td_body(const ll::Plan& P, const A& a, int B, int b) {
-    if (b >= B) return;
-    const int L = P.n_layers, NA = P.out[L - 1];
-    const float* q = a.scratch + ll::h_word(P, 0, L - 1, b, 0);
-    const float* qt = a.scratch + ll::h_word(P, 1, L - 1, b, 0);
-    float mx = qt[0];
-    for (int j = 1; j < NA; ++j) mx = qt[j] > mx ? qt[j] : mx;  // jnp.max
-    const int act = reinterpret_cast<const int32_t*>(a.scratch)[P.act_off + b];
-    const float rew = a.scratch[P.rew_off + b];
-    const float notdone = a.scratch[P.done_off + b] != 0.0f ? 0.0f : 1.0f;
-    const float td = rew + (a.gamma * mx) * notdone;
-    const bool ok = act >= 0 && act < NA;
-    float qa = td;
-    for (int j = 0; j < NA; ++j)
-        if (ok && j == act) qa = q[j];
-    const float d = qa - td;
-    const float w = a.weights[b];
-    a.scratch[P.sq_off + b] = w * (d * d);
-    float* dq = a.scratch + ll::d_word(P, L - 1, b, 0);
-    const float g = w * ((d + d) / (float)B);
-    for (int j = 0; j < P.ld[L - 1]; ++j) dq[j] = (ok && j == act) ? g : 0.0f;
-    a.absd[b] = __builtin_fabsf(d);
-    a.leaves[a.slots[b]] = 0.0f;
-}
-
+// The rows and the TD error are the uniform chain's bodies (ll::rows_body, ll::td_body) with the drawn rows as
+// their rows' policy (dronerl_learn_common.h).
+//
 // 6. The priorities (a workgroup of kThreads, every thread calls: barriers): row b's p = (|d| + eps)^alpha
 // (double, rounded once; at most 2^64, which a NaN becomes too) into its slot's leaf, which the TD kernel zeroed:
 // the largest over the rows that drew the slot.  pmax likewise (a workgroup's largest first, in LDS: wg_max).
-template <class A>
-__device__ __forceinline__ void priority_body(const A& a, int B, int b, uint32_t* wg_max) {
+__device__ __forceinline__ void priority_body(const Drawn& a, int B, int b, uint32_t* wg_max) {
     if (threadIdx.x == 0) *wg_max = 0u;
     __syncthreads();
     if (b < B) {

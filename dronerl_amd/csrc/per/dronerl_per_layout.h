@@ -134,15 +134,27 @@ struct SampleArgs {
     int64_t beta_steps;
 };
 
-// the learner's: the large-batch chain's arguments and the step's drawn rows
-struct LearnArgs : ll::LearnArgs {
-    const int64_t* slots;   // [batch]: the drawn slots
-    const float* weights;   // [batch]: their importance weights, w / wmax
-    float* absd;            // [batch]: |q - td| of the rows
-    float* leaves;          // tree + P: slot s's leaf is leaves[s]
+// One step's drawn rows and the tree's leaves, as the rows, the TD and the priority kernels of every prioritized
+// chain see them (dense, population member, conv): the rows' policy of dronerl_learn_common.h.
+struct Drawn {
+    const int64_t* slots;  // [batch]: the drawn slots
+    const float* weights;  // [batch]: their importance weights, w / wmax
+    float* absd;           // [batch]: |q - td| of the rows
+    float* leaves;         // tree + P: slot s's leaf is leaves[s]
     float* pmax;
     double alpha, per_eps;
 };
+
+DRL_PER_HD Drawn drawn_of(const TreeArgs& t, double alpha, double per_eps) {
+    return Drawn{t.slots, t.weights, t.absd, t.tree + t.P, t.pmax, alpha, per_eps};
+}
+
+// the learner's: the large-batch chain's arguments (the base: what the uniform kernels of the chain are launched
+// with) and the step's drawn rows
+struct LearnArgs : ll::LearnArgs {
+    Drawn d;
+};
+static_assert(sizeof(LearnArgs) <= 4096, "the arguments are read in place from the kernarg segment");
 
 // (hipError_t values) stream-ordered launches
 int launch_init(const TreeArgs& t, hipStream_t s);

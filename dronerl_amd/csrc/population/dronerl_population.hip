@@ -10,7 +10,9 @@
 //                              bodies the single-agent kernels run), a member per grid slice.  A member trains
 //                              iff size >= its batch, decided here on the device from its hyperparameter record;
 //                              rows at or beyond its batch do nothing; one that does not train still blends its
-//                              target when due, decays epsilon and advances its step.
+//                              target when due, decays epsilon and advances its step.  The prioritized
+//                              population (perpop/) has rows and TD kernels of its own and launches this
+//                              unit's forward, backward, update and counters kernels (launch_pop_*).
 // No workgroup waits for another, no float atomic is used, nothing reads host hyperparameters: a step is
 // graph-capturable.  Every loop bound comes from the validated plan.
 #include <hip/hip_runtime.h>
@@ -21,6 +23,7 @@
 #include "../dronerl_learn_common.h"
 #include "../largelearn/dronerl_largelearn_chain.h"
 #include "dronerl_population_layout.h"
+#include "dronerl_population_member.h"  // a member's view (shared with perpop/dronerl_perpop.hip)
 
 // every product and sum rounds on its own (no FMA contraction): the order oracle/dqn_learner.py restates
 #pragma clang fp contract(off)
@@ -31,72 +34,6 @@ namespace pop {
 namespace {
 
 using ll::ll_f4;
-
-// A member's view: the fields the chain's bodies and dronerl_learn_common.h read (ll::LearnArgs' names).
-struct Member {
-    int32_t batch, code_w;
-    float* online;
-    float* target;
-    float* adam_m;
-    float* adam_v;
-    DqnCounters* ctr;
-    float* scratch;
-    const uint32_t* r_obs;
-    const uint32_t* r_next;
-    int64_t row_words;
-    const int32_t* r_act;
-    const float* r_rew;
-    const uint8_t* r_done;
-    int64_t size;
-    uint64_t seed;
-    float gamma, b1, b2, c1, c2, adam_eps, neg_lr, tau, one_minus_tau, eps_decay, eps_end;
-    double b1d, b2d;
-    int32_t target_every, eps_every;
-};
-
-__device__ __forceinline__ const HRec& hrec(const uint8_t* base, int64_t hp_off, int m) {
-    return *reinterpret_cast<const HRec*>(base + hp_off + kHRecStride * m);
-}
-
-__device__ __forceinline__ Member member_of(const PopArgs& a, int m) {
-    const ll::Plan& P = a.P;
-    uint8_t* blk = a.base + a.stride * m;
-    const HRec& h = hrec(a.base, a.hp_off, m);
-    Member v;
-    v.batch = h.batch;
-    v.code_w = P.code_w;
-    v.online = reinterpret_cast<float*>(blk + P.pub.online_off);
-    v.target = reinterpret_cast<float*>(blk + P.pub.target_off);
-    v.adam_m = reinterpret_cast<float*>(blk + P.pub.m_off);
-    v.adam_v = reinterpret_cast<float*>(blk + P.pub.v_off);
-    v.ctr = reinterpret_cast<DqnCounters*>(blk + P.pub.counters_off);
-    v.scratch = reinterpret_cast<float*>(blk + P.pub.scratch_off);
-    const int64_t r0 = a.capacity * m;
-    v.r_obs = a.r_obs + r0 * a.row_words;
-    v.r_next = a.r_next + r0 * a.row_words;
-    v.row_words = a.row_words;
-    v.r_act = a.r_act + r0;
-    v.r_rew = a.r_rew + r0;
-    v.r_done = a.r_done + r0;
-    v.size = a.size;
-    v.seed = h.seed;
-    v.gamma = h.gamma;
-    v.b1 = h.b1;
-    v.b2 = h.b2;
-    v.c1 = h.c1;
-    v.c2 = h.c2;
-    v.adam_eps = h.adam_eps;
-    v.neg_lr = h.neg_lr;
-    v.tau = h.tau;
-    v.one_minus_tau = h.one_minus_tau;
-    v.eps_decay = h.eps_decay;
-    v.eps_end = h.eps_end;
-    v.b1d = h.b1d;
-    v.b2d = h.b2d;
-    v.target_every = h.target_every;
-    v.eps_every = h.eps_every;
-    return v;
-}
 
 // what dq_input reads of its argument block
 struct CodeRows {
@@ -265,7 +202,7 @@ __global__ void __launch_bounds__(kThreads) drl_pop_rows_kernel(PopArgs args) {
     const PopArgs& a = *(const PopArgs*)__builtin_amdgcn_kernarg_segment_ptr();
     const Member v = member_of(a, blockIdx.y);
     if (a.size < v.batch) return;
-    ll::rows_body(a.P, v, v.batch, (int64_t)blockIdx.x * kThreads + threadIdx.x);
+    ll::rows_body(a.P, v, UniformRows{}, v.batch, (int64_t)blockIdx.x * kThreads + threadIdx.x);
 }
 
 // 2. layer l's forward: grid (row tiles, 2 nets x members, unit tiles)
@@ -284,7 +221,7 @@ __global__ void __launch_bounds__(kThreads) drl_pop_td_kernel(PopArgs args) {
     const PopArgs& a = *(const PopArgs*)__builtin_amdgcn_kernarg_segment_ptr();
     const Member v = member_of(a, blockIdx.y);
     if (a.size < v.batch) return;
-    ll::td_body(a.P, v, v.batch, (int)(blockIdx.x * kThreads + threadIdx.x));
+    ll::td_body(a.P, v, UniformRows{}, v.batch, (int)(blockIdx.x * kThreads + threadIdx.x));
 }
 
 // 4. layer l's backward (l >= 1): grid (row tiles, members, unit tiles)
@@ -358,19 +295,24 @@ int launch_pop_add(const AddArgs& a, hipStream_t s) {
     return (int)hipGetLastError();
 }
 
-int launch_pop_train(const PopArgs& a, hipStream_t s) {
+// ---- the chain's segments: the launches the prioritized population's chain (perpop/dronerl_perpop.hip) takes
+// over as they are.  The grid arithmetic lives here alone; the caller reads hipGetLastError behind its last launch.
+// 2. every layer's forward
+void launch_pop_forward(const PopArgs& a, hipStream_t s) {
+    const ll::Plan& P = a.P;
+    const unsigned M = (unsigned)a.members;
+    for (int l = 0; l < P.n_layers; ++l)
+        hipLaunchKernelGGL(drl_pop_forward_kernel, dim3((unsigned)ll::row_tiles(P), 2 * M, (unsigned)ll::unit_tiles(P.out[l])),
+                           dim3(ll::kTileThreads), 0, s, a, l);
+}
+
+// 4.-5. the backward pass of every layer >= 1, then the update
+void launch_pop_backward_update(const PopArgs& a, hipStream_t s) {
     const ll::Plan& P = a.P;
     const unsigned M = (unsigned)a.members;
     const int L = P.n_layers;
-    const unsigned rt = (unsigned)ll::row_tiles(P);
-    const int64_t elems = 2 * (int64_t)P.batch * P.in4;
-    hipLaunchKernelGGL(drl_pop_rows_kernel, dim3((unsigned)((elems + kThreads - 1) / kThreads), M), dim3(kThreads), 0, s, a);
-    for (int l = 0; l < L; ++l)
-        hipLaunchKernelGGL(drl_pop_forward_kernel, dim3(rt, 2 * M, (unsigned)ll::unit_tiles(P.out[l])),
-                           dim3(ll::kTileThreads), 0, s, a, l);
-    hipLaunchKernelGGL(drl_pop_td_kernel, dim3((unsigned)((P.batch + kThreads - 1) / kThreads), M), dim3(kThreads), 0, s, a);
     for (int l = L - 1; l >= 1; --l)
-        hipLaunchKernelGGL(drl_pop_backward_kernel, dim3(rt, M, (unsigned)ll::unit_tiles(P.in[l])),
+        hipLaunchKernelGGL(drl_pop_backward_kernel, dim3((unsigned)ll::row_tiles(P), M, (unsigned)ll::unit_tiles(P.in[l])),
                            dim3(ll::kTileThreads), 0, s, a, l);
     int kt = 0, jt = 0;  // (the widest layer's tiles; a workgroup outside its layer's returns at once)
     for (int l = 0; l < L; ++l) {
@@ -379,7 +321,22 @@ int launch_pop_train(const PopArgs& a, hipStream_t s) {
     }
     hipLaunchKernelGGL(drl_pop_update_kernel, dim3((unsigned)kt, (unsigned)jt, (unsigned)L * M), dim3(ll::kUpdateThreads),
                        0, s, a);
-    hipLaunchKernelGGL(drl_pop_counters_kernel, dim3(M), dim3(kThreads), 0, s, a);
+}
+
+// 6. the counters
+void launch_pop_counters(const PopArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(drl_pop_counters_kernel, dim3((unsigned)a.members), dim3(kThreads), 0, s, a);
+}
+
+int launch_pop_train(const PopArgs& a, hipStream_t s) {
+    const ll::Plan& P = a.P;
+    const unsigned M = (unsigned)a.members;
+    const int64_t elems = 2 * (int64_t)P.batch * P.in4;
+    hipLaunchKernelGGL(drl_pop_rows_kernel, dim3((unsigned)((elems + kThreads - 1) / kThreads), M), dim3(kThreads), 0, s, a);
+    launch_pop_forward(a, s);
+    hipLaunchKernelGGL(drl_pop_td_kernel, dim3((unsigned)((P.batch + kThreads - 1) / kThreads), M), dim3(kThreads), 0, s, a);
+    launch_pop_backward_update(a, s);
+    launch_pop_counters(a, s);
     return (int)hipGetLastError();
 }
 

@@ -162,6 +162,12 @@ int launch_pop_init(const PopArgs& a, hipStream_t s);  // (the records are in pl
 int launch_pop_act(const ActArgs& a, int lds_bytes, hipStream_t s);
 int launch_pop_add(const AddArgs& a, hipStream_t s);
 int launch_pop_train(const PopArgs& a, hipStream_t s);
+// ... and the segments of that chain which the prioritized population's chain (perpop/) launches as they are:
+// every layer's forward; the backward pass and the update; the counters.  (No error is read: the caller reads
+// hipGetLastError behind its last launch.)
+void launch_pop_forward(const PopArgs& a, hipStream_t s);
+void launch_pop_backward_update(const PopArgs& a, hipStream_t s);
+void launch_pop_counters(const PopArgs& a, hipStream_t s);
 int launch_pop_sample(const PopArgs& a, hipStream_t s);
 
 }  // namespace pop

@@ -246,10 +246,6 @@ def test_routing_of_prioritized_learners_and_per_train_cli(monkeypatch):
 _T = "test_conv_per.py::"
 KERNEL_TESTS = {
     "drl_convnet_dqn_per_rows_kernel": _T + "test_learner_matches_the_restatement_per_step",
-    "drl_convnet_dqn_per_dense_grad_kernel": _T + "test_learner_matches_the_restatement_per_step",
-    "drl_convnet_dqn_per_conv_grad_kernel": _T + "test_learner_matches_the_restatement_per_step",
-    "drl_convnet_dqn_per_update_kernel": _T + "test_alpha0_beta0_is_the_uniform_conv_learner_bit_exact",
-    "drl_convnet_dqn_per_counters_kernel": _T + "test_without_a_sample_the_tree_is_left_alone",
     "drl_convnet_dqn_per_priority_kernel": _T + "test_a_slot_drawn_twice_takes_the_larger_priority",
 }
 

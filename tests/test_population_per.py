@@ -230,12 +230,8 @@ KERNEL_TESTS = {
     "drl_pop_per_rebuild_kernel": "test_population_per.py::test_member_trees_rebuild_to_the_numpy_tree_bit_exact",
     "drl_pop_per_sample_kernel": "test_population_per.py::test_member_samples_are_the_single_agents_bit_exact",
     "drl_pop_per_rows_kernel": "test_population_per.py::test_a_member_is_the_single_agent_bit_exact",
-    "drl_pop_per_forward_kernel": "test_population_per.py::test_a_member_is_the_single_agent_bit_exact",
     "drl_pop_per_td_kernel": "test_population_per.py::test_a_member_is_the_single_agent_bit_exact",
     "drl_pop_per_priority_kernel": "test_population_per.py::test_a_member_is_the_single_agent_bit_exact",
-    "drl_pop_per_backward_kernel": "test_population_per.py::test_a_member_is_the_single_agent_bit_exact",
-    "drl_pop_per_update_kernel": "test_population_per.py::test_a_member_is_the_single_agent_bit_exact",
-    "drl_pop_per_counters_kernel": "test_population_per.py::test_a_member_is_the_single_agent_bit_exact",
 }
 
 

@@ -238,14 +238,9 @@ KERNEL_TESTS = {
     "drl_per_rebuild_kernel": "test_prioritized_replay.py::test_tree_rebuild_is_the_numpy_tree_bit_exact",
     "drl_per_sample_kernel": "test_prioritized_replay.py::test_sample_is_the_stated_descent_and_weights_within_one_ulp",
     "drl_dqn_per_rows_kernel": "test_prioritized_replay.py::test_alpha0_beta0_is_the_oracle_bit_exact",
-    "drl_dqn_per_forward_kernel": "test_prioritized_replay.py::test_alpha0_beta0_is_the_oracle_bit_exact",
     "drl_dqn_per_td_kernel": "test_prioritized_replay.py::test_full_per_matches_the_restatement",
     "drl_dqn_per_priority_kernel": "test_prioritized_replay.py::test_full_per_matches_the_restatement",
-    "drl_dqn_per_backward_kernel": "test_prioritized_replay.py::test_alpha0_beta0_is_the_oracle_bit_exact",
-    "drl_dqn_per_update_kernel": "test_prioritized_replay.py::test_alpha0_beta0_is_the_oracle_bit_exact",
     # (every oracle case starts with a ring smaller than the batch: the target blend alone, when due)
-    "drl_dqn_per_blend_kernel": "test_prioritized_replay.py::test_alpha0_beta0_is_the_oracle_bit_exact",
-    "drl_dqn_per_counters_kernel": "test_prioritized_replay.py::test_alpha0_beta0_is_the_oracle_bit_exact",
 }
 
 
