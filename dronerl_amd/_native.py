@@ -65,6 +65,10 @@ EXPORTS = ["drl_abi_version", "drl_last_error", "drl_side_from_density", "drl_la
            # a population of dense DQN agents in one launch chain (dronerl_amd.population)
            "drl_pop_layout_query", "drl_pop_init", "drl_pop_act", "drl_pop_replay_add", "drl_pop_train",
            "drl_pop_sample_rows",
+           # Double DQN targets for the dense chains, uniform and prioritized, and per population member
+           # (DQNHParams.double_dqn)
+           "drl_dqn_double_train", "drl_widenet_dqn_double_train", "drl_dqn_double_per_train",
+           "drl_widenet_dqn_double_per_train", "drl_pop_double_train",
            # ... with prioritized replay, a tree and PER hyperparameters per member
            # (dronerl_amd.population.PrioritizedPopulationDQN)
            "drl_pop_per_layout_query", "drl_pop_per_init", "drl_pop_per_mark_new", "drl_pop_per_rebuild",

@@ -40,7 +40,9 @@ SOURCES = [os.path.join(CSRC, "dronerl_kernels.hip"), os.path.join(CSRC, "droner
            os.path.join(CSRC, "per", "dronerl_per.hip"), os.path.join(CSRC, "per", "dronerl_per_api.cpp"),
            os.path.join(CSRC, "perpop", "dronerl_perpop.hip"), os.path.join(CSRC, "perpop", "dronerl_perpop_api.cpp"),
            os.path.join(CSRC, "convper", "dronerl_convper.hip"),
-           os.path.join(CSRC, "convper", "dronerl_convper_api.cpp")]
+           os.path.join(CSRC, "convper", "dronerl_convper_api.cpp"),
+           os.path.join(CSRC, "doubledqn", "dronerl_doubledqn.hip"),
+           os.path.join(CSRC, "doubledqn", "dronerl_doubledqn_api.cpp")]
 DEPS = SOURCES + [os.path.join(CSRC, "dronerl_internal.h"), os.path.join(CSRC, "dronerl_act_common.h"),
                   os.path.join(CSRC, "dronerl_learn_common.h"), os.path.join(CSRC, "dronerl_learn_args.h"),
                   os.path.join(CSRC, "convlearn", "dronerl_convlearn_layout.h"),
@@ -52,6 +54,8 @@ DEPS = SOURCES + [os.path.join(CSRC, "dronerl_internal.h"), os.path.join(CSRC, "
                   os.path.join(CSRC, "largelearn", "dronerl_largelearn_chain.h"),
                   os.path.join(CSRC, "population", "dronerl_population_layout.h"),
                   os.path.join(CSRC, "population", "dronerl_population_member.h"),
+                  os.path.join(CSRC, "per", "dronerl_per_learn_args.h"),
+                  os.path.join(CSRC, "doubledqn", "dronerl_doubledqn.h"),
                   os.path.join(CSRC, "league", "dronerl_league_layout.h"),
                   os.path.join(CSRC, "convleague", "dronerl_convleague_layout.h"),
                   os.path.join(CSRC, "convleague", "dronerl_convleague_tile.h"),

@@ -57,6 +57,8 @@ def parse_args(argv=None):
     except json.JSONDecodeError as e:
         raise ValueError(f"--grid is not valid JSON: {e}")
     points = expand_grid(grid)
+    from .train import refuse_double_dqn
+    refuse_double_dqn(args, "conv self-play (conv_selfplay)", points)
     if len(points) not in (1, own.learners):
         raise ValueError(f"--grid has {len(points)} points: one per learner ({own.learners}) or one shared point")
     args.learners, args.drones_per_learner, args.drones = own.learners, own.drones_per_learner, drones

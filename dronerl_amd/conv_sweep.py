@@ -47,6 +47,8 @@ def parse_args(argv=None):
         raise ValueError("--members_seeds must be >= 1")
     args.members_seeds = own.members_seeds
     points = expand_grid(grid)
+    from .train import refuse_double_dqn
+    refuse_double_dqn(args, "the conv population sweep (conv_sweep)", points)
     from .population import POP_MAX_MEMBERS
     if len(points) * own.members_seeds > POP_MAX_MEMBERS:
         raise ValueError(f"the population has {len(points) * own.members_seeds} members; at most {POP_MAX_MEMBERS}")

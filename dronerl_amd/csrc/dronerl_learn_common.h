@@ -69,6 +69,42 @@ __device__ __forceinline__ void dq_row_keep(const Drawn& p, int b, float d) {
     dq_row_keep(p, b, p.slots[b], d);
 }
 
+// The target rule: which of the target net's next-state values a row's TD target takes.  The second compile-time
+// policy of the launch chains' TD body, next to the rows' policy:
+//   MaxTarget       max_a Q_target(next_obs) (dqn.py:160-167; jnp.max).  The selector's values are never read.
+//   DoubleTarget    Q_target(next_obs)[a*], a* = argmax_a Q_online(next_obs) (van Hasselt et al. 2016): the first
+//                   maximum, as jnp.argmax; a NaN never wins a comparison.  The selection is an index: no gradient
+//                   flows through the selector's values.
+// qt, qs: the target's and the selector's Q values of the row, A of them (A <= kTargetRuleActions).
+struct MaxTarget {};
+struct DoubleTarget {};
+constexpr int kTargetRuleActions = 8;  // drl_qnet_desc's limit on n_actions
+
+__device__ __forceinline__ float dq_next_value(const MaxTarget&, const float* qt, const float*, int A) {
+    float mx = qt[0];
+    for (int j = 1; j < A; ++j) mx = qt[j] > mx ? qt[j] : mx;  // jnp.max
+    return mx;
+}
+__device__ __forceinline__ float dq_next_value(const DoubleTarget&, const float* qt, const float* qs, int A) {
+    // a* = 0; for j = 1 .. A-1: if qs[j] > qs[a*]: a* = j -- with qs[a*] and qt[a*] carried instead of the index
+    float best = qs[0], v = qt[0];
+#pragma unroll
+    for (int j = 1; j < kTargetRuleActions; ++j)
+        if (j < A && qs[j] > best) {
+            best = qs[j];
+            v = qt[j];
+        }
+    return v;
+}
+
+// The selector's Q values of a row, read into registers (qs) from the words `from` before anything overwrites
+// them; the max rule has none to read.
+__device__ __forceinline__ void dq_selector_values(const MaxTarget&, float*, const float*, int) {}
+__device__ __forceinline__ void dq_selector_values(const DoubleTarget&, float* qs, const float* from, int A) {
+#pragma unroll
+    for (int j = 0; j < kTargetRuleActions; ++j) qs[j] = j < A ? from[j] : 0.0f;
+}
+
 // Input k of replay row s: a policy-code row is decoded with the channel rules
 // of the observation writer (wrappers.py:10-31; drl_code_decode), an f32 row read.
 template <class Args>

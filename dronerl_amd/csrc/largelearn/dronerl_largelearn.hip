@@ -110,6 +110,13 @@ __global__ void __launch_bounds__(kThreads) drl_dqn_large_sample_kernel(const Dq
 
 // ---- the chain's segments: the launches a prioritized chain (per/dronerl_per.hip) takes over as they are.  The
 // grid arithmetic lives here alone; the caller reads hipGetLastError behind its last launch.
+// 1. the rows (uniform draws), and the grid every chain's TD kernel takes: a thread per row
+void launch_large_rows(const LearnArgs& a, hipStream_t s) {
+    const int64_t elems = 2 * (int64_t)a.P.batch * a.P.in4;
+    hipLaunchKernelGGL(drl_dqn_large_rows_kernel, dim3((unsigned)((elems + kThreads - 1) / kThreads)), dim3(kThreads), 0,
+                       s, a);
+}
+
 // 2. every layer's forward
 void launch_large_forward(const LearnArgs& a, hipStream_t s) {
     const Plan& P = a.P;
@@ -149,8 +156,7 @@ int launch_large_train(const LearnArgs& a, hipStream_t s) {
     const Plan& P = a.P;
     const dim3 eb(kThreads);
     if (a.trained) {
-        const int64_t elems = 2 * (int64_t)P.batch * P.in4;
-        hipLaunchKernelGGL(drl_dqn_large_rows_kernel, dim3((unsigned)((elems + kThreads - 1) / kThreads)), eb, 0, s, a);
+        launch_large_rows(a, s);
         launch_large_forward(a, s);
         hipLaunchKernelGGL(drl_dqn_large_td_kernel, dim3((unsigned)((P.batch + kThreads - 1) / kThreads)), eb, 0, s, a);
         launch_large_backward_update(a, s);

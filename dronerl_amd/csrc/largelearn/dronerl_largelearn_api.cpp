@@ -30,42 +30,9 @@ int ll_plan(const drl_qnet_desc* d, int32_t batch, drl::QnetLayout* L, drl::ll::
 
 }  // namespace
 
-extern "C" {
-
-int drl_dqn_large_layout_query(const drl_qnet_desc* d, int32_t batch, drl_dqn_layout* layout) {
-    drl::QnetLayout L;
-    drl::ll::Plan P;
-    if (ll_plan(d, batch, &L, &P)) return -1;
-    if (!layout) return fail("layout is NULL");
-    *layout = P.pub;
-    return 0;
-}
-
-int drl_dqn_large_init(const drl_qnet_desc* d, int32_t batch, void* d_agent, float epsilon_start, hipStream_t stream) {
-    drl::QnetLayout L;
-    drl::ll::Plan P;
-    if (ll_plan(d, batch, &L, &P)) return -1;
-    if (!d_agent || (uintptr_t)d_agent % 16) return fail("the agent block must be a 16-byte aligned device pointer");
-    uint8_t* base = static_cast<uint8_t*>(d_agent);
-    // the moments; the init kernel sets the counters.  The scratch needs no clearing: every word a launch reads
-    // was written by a launch before it in the same step.
-    if (hipError_t e = hipMemsetAsync(base + P.pub.m_off, 0, (size_t)(P.pub.counters_off - P.pub.m_off), stream);
-        e != hipSuccess)
-        return hip_fail((int)e, "drl_dqn_large_init moments");
-    hipError_t e = drl::launch_dqn_init(base + P.pub.counters_off, epsilon_start, stream);
-    return e == hipSuccess ? 0 : hip_fail((int)e, "drl_dqn_large_init launch");
-}
-
-int drl_dqn_large_train(const drl_qnet_desc* d, const drl_dqn_hparams* h, void* d_agent, void* d_packed,
-                        const drl_replay* r, int64_t size, hipStream_t stream) {
-    drl::QnetLayout L;
-    drl::ll::LearnArgs a;
-    memset(&a, 0, sizeof a);
-    if (!h) {
-        if (ll_plan(d, 1, &L, &a.P)) return -1;
-        return fail("hparams is NULL");
-    }
-    if (ll_plan(d, h->batch, &L, &a.P)) return -1;
+// drl_dqn_large_train's checks behind its plan (a.P), then everything of the argument block but pack_status
+int drl::ll::large_train_args(LearnArgs& a, int in_features, const drl_dqn_hparams* h, void* d_agent, void* d_packed,
+                              const drl_replay* r, int64_t size) {
     const drl::ll::Plan& P = a.P;
     if (h->target_update_interval < 1 || h->epsilon_decay_every < 1)
         return fail("target_update_interval and epsilon_decay_every must be >= 1");
@@ -79,7 +46,7 @@ int drl_dqn_large_train(const drl_qnet_desc* d, const drl_dqn_hparams* h, void* 
     if (P.code_w) {
         if ((int64_t)r->obs_floats * 4 != drl::lay::code_bytes(P.code_w))
             return fail("a DRL_QNET_INPUT_CODE net's replay rows are policy codes (drl_policy_code_bytes / 4 words)");
-    } else if (r->obs_floats < d->in_features) {
+    } else if (r->obs_floats < in_features) {
         return fail("replay obs_floats < in_features");
     }
     if ((uintptr_t)r->obs % 4 || (uintptr_t)r->next_obs % 4) return fail("replay rows must be 4-byte aligned");
@@ -116,6 +83,47 @@ int drl_dqn_large_train(const drl_qnet_desc* d, const drl_dqn_hparams* h, void* 
     a.b2d = h->beta2;
     a.target_every = h->target_update_interval;
     a.eps_every = h->epsilon_decay_every;
+    return 0;
+}
+
+extern "C" {
+
+int drl_dqn_large_layout_query(const drl_qnet_desc* d, int32_t batch, drl_dqn_layout* layout) {
+    drl::QnetLayout L;
+    drl::ll::Plan P;
+    if (ll_plan(d, batch, &L, &P)) return -1;
+    if (!layout) return fail("layout is NULL");
+    *layout = P.pub;
+    return 0;
+}
+
+int drl_dqn_large_init(const drl_qnet_desc* d, int32_t batch, void* d_agent, float epsilon_start, hipStream_t stream) {
+    drl::QnetLayout L;
+    drl::ll::Plan P;
+    if (ll_plan(d, batch, &L, &P)) return -1;
+    if (!d_agent || (uintptr_t)d_agent % 16) return fail("the agent block must be a 16-byte aligned device pointer");
+    uint8_t* base = static_cast<uint8_t*>(d_agent);
+    // the moments; the init kernel sets the counters.  The scratch needs no clearing: every word a launch reads
+    // was written by a launch before it in the same step.
+    if (hipError_t e = hipMemsetAsync(base + P.pub.m_off, 0, (size_t)(P.pub.counters_off - P.pub.m_off), stream);
+        e != hipSuccess)
+        return hip_fail((int)e, "drl_dqn_large_init moments");
+    hipError_t e = drl::launch_dqn_init(base + P.pub.counters_off, epsilon_start, stream);
+    return e == hipSuccess ? 0 : hip_fail((int)e, "drl_dqn_large_init launch");
+}
+
+int drl_dqn_large_train(const drl_qnet_desc* d, const drl_dqn_hparams* h, void* d_agent, void* d_packed,
+                        const drl_replay* r, int64_t size, hipStream_t stream) {
+    drl::QnetLayout L;
+    drl::ll::LearnArgs a;
+    memset(&a, 0, sizeof a);
+    if (!h) {
+        if (ll_plan(d, 1, &L, &a.P)) return -1;
+        return fail("hparams is NULL");
+    }
+    if (ll_plan(d, h->batch, &L, &a.P)) return -1;
+    if (drl::ll::large_train_args(a, d->in_features, h, d_agent, d_packed, r, size)) return -1;
+    const drl::ll::Plan& P = a.P;
     // the act's image of the new online set: the pack kernel itself on the online set, so the image is a fresh
     // drl_qnet_pack's byte for byte.  drl_qnet_pack clears the status vector with a hipMemsetAsync; here the
     // counters kernel stores the zeros instead, so that a captured call holds kernel nodes only.

@@ -111,20 +111,18 @@ __device__ __forceinline__ void rows_body(const Plan& P, const A& a, const R& p,
 // 2. Layer l of net n (0 the online net on obs, 1 the target net on next_obs), row tile bx, unit tile bz:
 // z[b][j] = dot(x[b], W[j]) + bias[j]; a hidden layer stores relu(z), the Q head z.  Xs: kTileRows * kChunkStride
 // floats of LDS.
-template <class A>
-__device__ __forceinline__ void forward_body(const Plan& P, const A& a, int B, int l, int n, int bx, int bz,
-                                             float* Xs) {
+// The tile itself, once the pass is chosen: parameter set `set` on the rows X (stride lda), into the rows of
+// ld[l] words at scratch word `out_off`.
+__device__ __forceinline__ void forward_tile(const Plan& P, int B, int l, const float* set, const float* X, int lda,
+                                             float* scratch, int64_t out_off, int bx, int bz, float* Xs) {
     const int K = P.in[l], J = P.out[l];
-    const float* set = n ? a.target : a.online;
-    const float* X = a.scratch + (l == 0 ? P.x_off[n] : P.h_off[n][l - 1]);
-    const int lda = l == 0 ? P.in4 : P.ld[l - 1];
     float z[kUnitsPerWave];
     ll_tile(X, lda, K, set + P.woff[l], 1, K, J, B, bx, bz, Xs, z);
     const int b = bx * kTileRows + (threadIdx.x & 63);
     const int j0 = bz * kTileUnits + (threadIdx.x >> 6) * kUnitsPerWave;
     if (b >= B) return;
     const float* bias = set + P.boff[l];
-    float* out = a.scratch + h_word(P, n, l, b, 0);
+    float* out = scratch + (out_off + (int64_t)b * P.ld[l]);
     const bool hidden = l + 1 < P.n_layers;
 #pragma unroll
     for (int u = 0; u < kUnitsPerWave; ++u) {
@@ -135,18 +133,43 @@ __device__ __forceinline__ void forward_body(const Plan& P, const A& a, int B, i
     }
 }
 
+template <class A>
+__device__ __forceinline__ void forward_body(const Plan& P, const A& a, int B, int l, int n, int bx, int bz,
+                                             float* Xs) {
+    const float* set = n ? a.target : a.online;
+    const float* X = a.scratch + (l == 0 ? P.x_off[n] : P.h_off[n][l - 1]);
+    const int lda = l == 0 ? P.in4 : P.ld[l - 1];
+    forward_tile(P, B, l, set, X, lda, a.scratch, P.h_off[n][l], bx, bz, Xs);
+}
+
+// 2b. Layer l of the Double DQN selector: the online net on next_obs, a third pass beside forward_body's two in
+// the same launches.  Its activations live in the delta words d_off[l] ([batch][ld[l]], the shape of h_off[n][l]):
+// nothing reads those between a step's rows launch and its TD launch, which takes the Q head's values into
+// registers before it stores the deltas there; the backward launches then overwrite the layers below.
+template <class A>
+__device__ __forceinline__ void selector_body(const Plan& P, const A& a, int B, int l, int bx, int bz, float* Xs) {
+    const float* X = a.scratch + (l == 0 ? P.x_off[1] : P.d_off[l - 1]);
+    const int lda = l == 0 ? P.in4 : P.ld[l - 1];
+    forward_tile(P, B, l, a.online, X, lda, a.scratch, P.d_off[l], bx, bz, Xs);
+}
+
 // 3. The TD error of row b (dqn.py:147-183): td = r + gamma * max_a Q_target * (1 - done), d = q[a] - td, the
 // row's squared error and the Q head's deltas d loss / d q[b][a_b] = 2 d / B, both under the row's importance
 // weight when p is a prioritized draw (dq_row_weight), which also keeps |d| and zeroes the slot's leaf
-// (dq_row_keep).  An action outside [0, A) adds nothing (d = 0, no delta), as in drl_dqn_train.
-template <class A, class R>
-__device__ __forceinline__ void td_body(const Plan& P, const A& a, const R& p, int B, int b) {
+// (dq_row_keep).  An action outside [0, A) adds nothing (d = 0, no delta), as in drl_dqn_train.  T: the target
+// rule (dronerl_learn_common.h).  Under DoubleTarget the next state's value is the target's at the selector's
+// first maximum; the selector's Q values are the words selector_body left where the Q head's deltas go, read
+// into registers before those stores.
+template <class A, class R, class T = MaxTarget>
+__device__ __forceinline__ void td_body(const Plan& P, const A& a, const R& p, int B, int b, const T& rule = T{}) {
     if (b >= B) return;
     const int L = P.n_layers, NA = P.out[L - 1];
+    static_assert(kMaxActions <= kTargetRuleActions, "the target rule's scan covers every action");
     const float* q = a.scratch + h_word(P, 0, L - 1, b, 0);
     const float* qt = a.scratch + h_word(P, 1, L - 1, b, 0);
-    float mx = qt[0];
-    for (int j = 1; j < NA; ++j) mx = qt[j] > mx ? qt[j] : mx;  // jnp.max
+    float qs[kTargetRuleActions];
+    dq_selector_values(rule, qs, a.scratch + d_word(P, L - 1, b, 0), NA);
+    const float mx = dq_next_value(rule, qt, qs, NA);
     const int act = reinterpret_cast<const int32_t*>(a.scratch)[P.act_off + b];
     const float rew = a.scratch[P.rew_off + b];
     const float notdone = a.scratch[P.done_off + b] != 0.0f ? 0.0f : 1.0f;

@@ -128,6 +128,20 @@ int launch_sample(const TreeArgs& t, const SampleArgs& a, const void* counters, 
     return (int)hipGetLastError();
 }
 
+// ---- the chain's segments which the Double DQN chain (doubledqn/) launches as they are: the rows at the drawn
+// slots, and the priorities behind a TD launch.  (No error is read: the caller reads hipGetLastError behind its
+// last launch.)
+void launch_per_rows(const LearnArgs& a, hipStream_t s) {
+    const int64_t elems = 2 * (int64_t)a.P.batch * a.P.in4;
+    hipLaunchKernelGGL(drl_dqn_per_rows_kernel, dim3((unsigned)((elems + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
+                       a);
+}
+
+void launch_per_priority(const LearnArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(drl_dqn_per_priority_kernel, dim3((unsigned)((a.P.batch + kThreads - 1) / kThreads)),
+                       dim3(kThreads), 0, s, a);
+}
+
 // The uniform chain (ll::launch_large_train) on the drawn rows: rebuild and sample in front, this unit's rows and
 // TD kernels in place of the uniform ones, the priorities behind the TD; every other launch is the uniform
 // chain's own kernel with the uniform arguments (a's base).
@@ -138,11 +152,10 @@ int launch_per_train(const LearnArgs& a, const TreeArgs& t, const SampleArgs& sa
         if (const int e = launch_rebuild(t, s)) return e;
         if (const int e = launch_sample(t, sa, a.ctr, s)) return e;
         const unsigned bt = (unsigned)((P.batch + kThreads - 1) / kThreads);
-        const int64_t elems = 2 * (int64_t)P.batch * P.in4;
-        hipLaunchKernelGGL(drl_dqn_per_rows_kernel, dim3((unsigned)((elems + kThreads - 1) / kThreads)), eb, 0, s, a);
+        launch_per_rows(a, s);
         ll::launch_large_forward(a, s);
         hipLaunchKernelGGL(drl_dqn_per_td_kernel, dim3(bt), eb, 0, s, a);
-        hipLaunchKernelGGL(drl_dqn_per_priority_kernel, dim3(bt), eb, 0, s, a);
+        launch_per_priority(a, s);
         ll::launch_large_backward_update(a, s);
     } else {
         ll::launch_large_blend(a, s);

@@ -11,6 +11,7 @@
 #include "../largelearn/dronerl_largelearn_layout.h"
 #include "../widenet/dronerl_widenet_layout.h"
 #include "dronerl_per_layout.h"
+#include "dronerl_per_learn_args.h"
 
 extern "C" __attribute__((visibility("hidden"))) int drl_internal_fail(const char* msg);
 
@@ -46,19 +47,8 @@ int per_hparams(const drl_per_hparams* ph) {
 int per_learn_args(drl::per::LearnArgs& a, int in_features, const drl_dqn_hparams* h, const drl_per_hparams* ph,
                    void* d_agent, void* d_packed, const drl_replay* r, int64_t size, void* d_per,
                    drl::per::TreeArgs* t, drl::per::SampleArgs* sa) {
-    const drl::ll::Plan& P = a.P;
-    if (per_hparams(ph)) return -1;
-    if (const char* msg = drl::check_learn_call(h, d_agent, d_packed, r)) return fail(msg);
-    drl::per::Plan T;
-    if (per_block(r->capacity, h->batch, d_per, &T)) return -1;
-    if (size < 0 || size > r->capacity) return fail("size must be in [0, capacity]");
-    if (const char* msg = drl::check_learn_rows(r, P.code_w, in_features, "replay obs_floats < in_features"))
-        return fail(msg);
-    drl::fill_learn_args(a, P.pub, P.code_w, h, d_agent, r, size);
-    *t = drl::per::tree_args(T, d_per);
-    a.d = drl::per::drawn_of(*t, ph->alpha, ph->eps);
-    *sa = drl::per::SampleArgs{h->sample_seed, size, ph->beta0, ph->beta_steps};
-    return 0;
+    const char* msg = drl::per::learn_args(a, in_features, h, ph, d_agent, d_packed, r, size, d_per, t, sa);
+    return msg ? fail(msg) : 0;
 }
 
 }  // namespace

@@ -164,6 +164,10 @@ int launch_sample(const TreeArgs& t, const SampleArgs& a, const void* counters, 
 // one learner step without the pack: rebuild, sample, the chain with the priority update (a.trained), or the
 // chain's no-sample step
 int launch_per_train(const LearnArgs& a, const TreeArgs& t, const SampleArgs& sa, hipStream_t s);
+// ... and the segments of that chain which the Double DQN chain (doubledqn/) launches as they are: the rows at the
+// drawn slots; the priorities.  (No error is read: the caller reads hipGetLastError behind its last launch.)
+void launch_per_rows(const LearnArgs& a, hipStream_t s);
+void launch_per_priority(const LearnArgs& a, hipStream_t s);
 
 }  // namespace per
 }  // namespace drl

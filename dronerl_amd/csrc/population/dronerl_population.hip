@@ -297,6 +297,13 @@ int launch_pop_add(const AddArgs& a, hipStream_t s) {
 
 // ---- the chain's segments: the launches the prioritized population's chain (perpop/dronerl_perpop.hip) takes
 // over as they are.  The grid arithmetic lives here alone; the caller reads hipGetLastError behind its last launch.
+// 1. the rows (uniform draws)
+void launch_pop_rows(const PopArgs& a, hipStream_t s) {
+    const int64_t elems = 2 * (int64_t)a.P.batch * a.P.in4;
+    hipLaunchKernelGGL(drl_pop_rows_kernel, dim3((unsigned)((elems + kThreads - 1) / kThreads), (unsigned)a.members),
+                       dim3(kThreads), 0, s, a);
+}
+
 // 2. every layer's forward
 void launch_pop_forward(const PopArgs& a, hipStream_t s) {
     const ll::Plan& P = a.P;
@@ -331,8 +338,7 @@ void launch_pop_counters(const PopArgs& a, hipStream_t s) {
 int launch_pop_train(const PopArgs& a, hipStream_t s) {
     const ll::Plan& P = a.P;
     const unsigned M = (unsigned)a.members;
-    const int64_t elems = 2 * (int64_t)P.batch * P.in4;
-    hipLaunchKernelGGL(drl_pop_rows_kernel, dim3((unsigned)((elems + kThreads - 1) / kThreads), M), dim3(kThreads), 0, s, a);
+    launch_pop_rows(a, s);
     launch_pop_forward(a, s);
     hipLaunchKernelGGL(drl_pop_td_kernel, dim3((unsigned)((P.batch + kThreads - 1) / kThreads), M), dim3(kThreads), 0, s, a);
     launch_pop_backward_update(a, s);

@@ -69,6 +69,17 @@ void fill_rings(drl::pop::PopArgs* a, const drl_replay* r, int64_t size) {
 
 }  // namespace
 
+// drl_pop_train's checks behind its plan, then its argument block: for drl_pop_train and for the calls that run
+// its chain with kernels of their own (doubledqn/).  0, or -1 with the message set.
+int drl::pop::pop_train_args(PopArgs* a, const Plan& P, void* d_pop, const drl_replay* r, int64_t size) {
+    if (check_block(d_pop)) return -1;
+    if (check_rings(P, r)) return -1;
+    if (size < 0 || size > r->capacity) return fail("size must be in [0, capacity]");
+    fill(a, P, d_pop);
+    fill_rings(a, r, size);
+    return 0;
+}
+
 extern "C" {
 
 int drl_pop_layout_query(const drl_widenet_desc* d, int32_t members, int32_t max_batch, drl_pop_layout* layout) {
@@ -203,12 +214,8 @@ int drl_pop_train(const drl_widenet_desc* d, int32_t members, int32_t max_batch,
                   int64_t size, hipStream_t stream) {
     drl::pop::Plan P;
     if (pop_plan(d, members, max_batch, &P)) return -1;
-    if (check_block(d_pop)) return -1;
-    if (check_rings(P, r)) return -1;
-    if (size < 0 || size > r->capacity) return fail("size must be in [0, capacity]");
     drl::pop::PopArgs a;
-    fill(&a, P, d_pop);
-    fill_rings(&a, r, size);
+    if (drl::pop::pop_train_args(&a, P, d_pop, r, size)) return -1;
     const int e = drl::pop::launch_pop_train(a, stream);
     return e == 0 ? 0 : hip_fail(e, "drl_pop_train launch");
 }

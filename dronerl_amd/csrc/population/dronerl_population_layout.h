@@ -164,11 +164,16 @@ int launch_pop_add(const AddArgs& a, hipStream_t s);
 int launch_pop_train(const PopArgs& a, hipStream_t s);
 // ... and the segments of that chain which the prioritized population's chain (perpop/) launches as they are:
 // every layer's forward; the backward pass and the update; the counters.  (No error is read: the caller reads
-// hipGetLastError behind its last launch.)
+// hipGetLastError behind its last launch.)  The Double DQN population's chain (doubledqn/) takes the rows too.
+void launch_pop_rows(const PopArgs& a, hipStream_t s);
 void launch_pop_forward(const PopArgs& a, hipStream_t s);
 void launch_pop_backward_update(const PopArgs& a, hipStream_t s);
 void launch_pop_counters(const PopArgs& a, hipStream_t s);
 int launch_pop_sample(const PopArgs& a, hipStream_t s);
+// (host, dronerl_population_api.cpp) drl_pop_train's checks behind its plan, then its argument block: 0, or -1 with
+// the message for drl_last_error set
+__attribute__((visibility("hidden"))) int pop_train_args(PopArgs* a, const Plan& P, void* d_pop, const drl_replay* r,
+                                                         int64_t size);
 
 }  // namespace pop
 }  // namespace drl

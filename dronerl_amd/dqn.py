@@ -115,6 +115,9 @@ def _bind(L):
         "drl_per_sample": [i64, i32, _vp, ctypes.POINTER(DrlPerHParams), u64, _vp, i64, _vp],
         "drl_dqn_per_train": [D, ctypes.POINTER(DrlDqnHParams), ctypes.POINTER(DrlPerHParams), _vp, _vp,
                               ctypes.POINTER(DrlReplay), i64, _vp, _vp],
+        "drl_dqn_double_train": [D, ctypes.POINTER(DrlDqnHParams), _vp, _vp, ctypes.POINTER(DrlReplay), i64, _vp],
+        "drl_dqn_double_per_train": [D, ctypes.POINTER(DrlDqnHParams), ctypes.POINTER(DrlPerHParams), _vp, _vp,
+                                     ctypes.POINTER(DrlReplay), i64, _vp, _vp],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -592,6 +595,10 @@ def _bind_widenet(L):
         "drl_widenet_dqn_sample_rows": [D, ctypes.POINTER(DrlDqnHParams), _vp, i64, _vp, _vp],
         "drl_widenet_dqn_per_train": [D, ctypes.POINTER(DrlDqnHParams), ctypes.POINTER(DrlPerHParams), _vp, _vp,
                                       ctypes.POINTER(DrlReplay), i64, _vp, _vp],
+        "drl_widenet_dqn_double_train": [D, ctypes.POINTER(DrlDqnHParams), _vp, _vp, ctypes.POINTER(DrlReplay), i64,
+                                         _vp],
+        "drl_widenet_dqn_double_per_train": [D, ctypes.POINTER(DrlDqnHParams), ctypes.POINTER(DrlPerHParams), _vp, _vp,
+                                             ctypes.POINTER(DrlReplay), i64, _vp, _vp],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -909,7 +916,12 @@ class DQNHParams:
     """The learner's hyperparameters: jax_impl/agents/dqn.py DQNAgentParams
     (:20-33) with train_jax.py's defaults (:349-360) and optax.adam's
     (b1 0.9, b2 0.999, eps 1e-8).  `epsilon_decay` None: train_jax.py:133-134's
-    value for `num_steps` (half the way to epsilon_end after 20 % of them)."""
+    value for `num_steps` (half the way to epsilon_end after 20 % of them).
+    `double_dqn`: the TD target takes the target net's value at the online
+    net's first maximum on next_obs (van Hasselt et al. 2016) instead of the
+    target net's maximum; a choice of the learner call, not a field of
+    drl_dqn_hparams (`c()` is the same under both rules).  The dense launch
+    chains train it; every other learner refuses it by name."""
     batch: int = 8
     gamma: float = 0.9
     learning_rate: float = 1e-3
@@ -924,6 +936,7 @@ class DQNHParams:
     epsilon_decay_every: int = 5
     num_steps: int = 1000
     sample_seed: int = 0
+    double_dqn: bool = False
 
     def decay(self) -> float:
         if self.epsilon_decay is not None:
@@ -934,6 +947,12 @@ class DQNHParams:
         return DrlDqnHParams(self.batch, self.target_update_interval, self.epsilon_decay_every, 0, self.gamma,
                              self.learning_rate, self.beta1, self.beta2, self.adam_eps, self.tau, self.decay(),
                              self.epsilon_end, self.sample_seed & (2**64 - 1))
+
+
+DOUBLE_SINGLE_LAUNCH_REFUSAL = ("double_dqn: the single-launch DQNLearner (drl_dqn_train) has no selector forward; "
+                                "make_learner picks LargeBatchDQNLearner, which trains Double DQN at every batch")
+DOUBLE_CONV_REFUSAL = ("double_dqn: the conv learners (ConvDQNLearner, LargeBatchConvDQNLearner, "
+                       "PrioritizedConvDQNLearner) train the max rule only: Double DQN is implemented for dense nets")
 
 
 class DQNLearner:
@@ -956,6 +975,8 @@ class DQNLearner:
     def __init__(self, net: QNetwork, hp: Optional[DQNHParams] = None, target=None,
                  generator: Optional[torch.Generator] = None):
         self.net, self.hp = net, hp or DQNHParams()
+        if self.hp.double_dqn:
+            raise ValueError(DOUBLE_SINGLE_LAUNCH_REFUSAL)
         self.L = net.L
         lay = DrlDqnLayout()
         _check(self.L, self.L.drl_dqn_layout_query(ctypes.byref(net.desc), self.hp.batch, ctypes.byref(lay)))
@@ -1083,12 +1104,17 @@ class LargeBatchDQNLearner(DQNLearner):
     chain of stream-ordered launches (drl_dqn_large_train: rows, each layer's
     forward, TD, each layer's backward, update, counters, re-pack) with no
     synchronisation and no wait between workgroups, so `train` is
-    graph-capturable.  The surface is DQNLearner's without `train(fresh=)`."""
+    graph-capturable.  The surface is DQNLearner's without `train(fresh=)`.
+    With hp.double_dqn the step is drl_dqn_double_train: the same chain,
+    launch for launch, with the Double DQN target."""
 
     _abi = "drl_dqn_large"  # the C calls: <_abi>_layout_query, _init, _train, _sample_rows
+    _double_train = "drl_dqn_double_train"  # ... and the train call under hp.double_dqn
     _bound = staticmethod(_bind)
 
     def _call(self, name):
+        if name == "train" and self.hp.double_dqn:
+            return getattr(self.L, self._double_train)
         return getattr(self.L, f"{self._abi}_{name}")
 
     def __init__(self, net: QNetwork, hp: Optional[DQNHParams] = None, target=None,
@@ -1173,6 +1199,7 @@ class WideDQNLearner(LargeBatchDQNLearner):
     refreshed by the wide pack kernel in the same call."""
 
     _abi = "drl_widenet_dqn"
+    _double_train = "drl_widenet_dqn_double_train"
     _bound = staticmethod(lambda L: _bind_widenet(_bind(L)))
 
 
@@ -1314,10 +1341,11 @@ class PrioritizedDQNLearner(LargeBatchDQNLearner):
         if per.rb.obs.device != self.block.device:
             raise ValueError("the replay buffer must be on the learner's device")
         per.bind(self.hp.batch)
-        _check(self.L, self.L.drl_dqn_per_train(ctypes.byref(self.net.desc), ctypes.byref(self._hp),
-                                                ctypes.byref(per._hp), _vp(self.block.data_ptr()),
-                                                _vp(self.net.packed.data_ptr()), ctypes.byref(per.rb._c), per.rb.size,
-                                                _vp(per.block.data_ptr()), _stream(self.block.device)))
+        call = self.L.drl_dqn_double_per_train if self.hp.double_dqn else self.L.drl_dqn_per_train
+        _check(self.L, call(ctypes.byref(self.net.desc), ctypes.byref(self._hp),
+                            ctypes.byref(per._hp), _vp(self.block.data_ptr()), _vp(self.net.packed.data_ptr()),
+                            ctypes.byref(per.rb._c), per.rb.size, _vp(per.block.data_ptr()),
+                            _stream(self.block.device)))
 
     def sample_slots(self, per: "PrioritizedReplay", out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The replay slots (int64 [batch]) the next train(per) draws: a
@@ -1343,6 +1371,7 @@ class _PrioritizedTrain:
     `_per_train`'s, the block and everything else the uniform learner's."""
 
     _per_train = None  # the C call's name
+    _double_per_train = None  # ... under hp.double_dqn (None: the family has no Double DQN chain)
 
     def train(self, per: "PrioritizedReplay"):
         """One learner block on the prioritized replay's current contents."""
@@ -1351,7 +1380,7 @@ class _PrioritizedTrain:
         if per.rb.obs.device != self.block.device:
             raise ValueError("the replay buffer must be on the learner's device")
         per.bind(self.hp.batch)
-        _check(self.L, getattr(self.L, self._per_train)(
+        _check(self.L, getattr(self.L, self._double_per_train if self.hp.double_dqn else self._per_train)(
             ctypes.byref(self.net.desc), ctypes.byref(self._hp), ctypes.byref(per._hp), _vp(self.block.data_ptr()),
             _vp(self.net.packed.data_ptr()), ctypes.byref(per.rb._c), per.rb.size, _vp(per.block.data_ptr()),
             _stream(self.block.device)))
@@ -1385,12 +1414,13 @@ class PrioritizedWideDQNLearner(_PrioritizedTrain, WideDQNLearner):
     inherited."""
 
     _per_train = "drl_widenet_dqn_per_train"
+    _double_per_train = "drl_widenet_dqn_double_per_train"
 
 
 def make_learner(net, hp: Optional[DQNHParams] = None, per: bool = False, **kw):
     """A net's learner: for a QNetwork by hp.batch, DQNLearner (one launch,
     batches up to 64) or LargeBatchDQNLearner (a launch chain, batches up to
-    4096); for a WideQNetwork, WideDQNLearner (the launch chain at every
+    4096, and every batch with hp.double_dqn); for a WideQNetwork, WideDQNLearner (the launch chain at every
     batch); for a ConvQNetwork by hp.batch, ConvDQNLearner (batches up to 64)
     or LargeBatchConvDQNLearner (chunked gradients, batches up to 4096).
     per=True: PrioritizedDQNLearner at every batch (a QNetwork only)."""
@@ -1404,7 +1434,8 @@ def make_learner(net, hp: Optional[DQNHParams] = None, per: bool = False, **kw):
     if isinstance(net, ConvQNetwork):
         cls = ConvDQNLearner if hp.batch <= CONV_DQN_MAX_BATCH else LargeBatchConvDQNLearner
         return cls(net, hp, **kw)
-    cls = DQNLearner if hp.batch <= DQN_MAX_BATCH else LargeBatchDQNLearner
+    # (the single-launch learner has no selector forward: Double DQN takes the chain at every batch)
+    cls = DQNLearner if hp.batch <= DQN_MAX_BATCH and not hp.double_dqn else LargeBatchDQNLearner
     return cls(net, hp, **kw)
 
 
@@ -1431,6 +1462,8 @@ class ConvDQNLearner:
     def __init__(self, net: ConvQNetwork, hp: Optional[DQNHParams] = None, target=None,
                  generator: Optional[torch.Generator] = None):
         self.net, self.hp = net, hp or DQNHParams()
+        if self.hp.double_dqn:
+            raise ValueError(DOUBLE_CONV_REFUSAL)
         self.L = _bind(_bind_convnet(net.L))
         lay = DrlConvnetDqnLayout()
         if self._call("layout_query")(ctypes.byref(net.desc), self.hp.batch, ctypes.byref(lay)):

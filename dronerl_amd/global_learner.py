@@ -60,6 +60,10 @@ def exchange_rows(packed: torch.Tensor, owner: torch.Tensor, world: int, group=N
     return stacked[owner.to(packed.device), torch.arange(packed.shape[0], device=packed.device)]
 
 
+DOUBLE_SHARDED_REFUSAL = ("double_dqn: a sharded run's learners train the max rule only (Double DQN is implemented "
+                          "for one GPU's dense learners)")
+
+
 class ShardedReplay:
     """This rank's image of the one global replay ring (see the module
     docstring).  `add_many` takes this shard's rows exactly as
@@ -116,6 +120,8 @@ class ShardedReplay:
         """Land in this image, at the slots the learner's next step draws,
         the rows their owners hold (nothing when the ring cannot sample yet:
         buffers.py can_sample; nothing to do on one rank)."""
+        if getattr(learner.hp, "double_dqn", False) and self.world > 1:
+            raise ValueError(DOUBLE_SHARDED_REFUSAL)
         if self.world == 1 or self.ring.size < learner.hp.batch:
             return
         if slots is None:

@@ -125,12 +125,18 @@ class LeagueReplay(PopulationReplay):
         self.size = min(self.size + E, self.capacity)
 
 
+DOUBLE_LEAGUE_REFUSAL = ("double_dqn: a league's learners (LeagueDQN, ConvLeagueDQN) train the max rule only; Double "
+                         "DQN is implemented for single dense agents and dense populations")
+
+
 class LeagueDQN(PopulationDQN):
     """K learners over the same E envs, learner k on drone index k: a
     PopulationDQN with members = K and envs_per_member = E whose act reads
     block k of every drone's code and writes column k of the action matrix
     (drl_league_act).  `train`, `member_net`, `save`, `params`, `counters`
     and `sample_slots` are the population's."""
+
+    _double_refusal = DOUBLE_LEAGUE_REFUSAL
 
     def __init__(self, in_features: int, hidden: Sequence[int], hps: Sequence[DQNHParams], num_envs: int, **kw):
         super().__init__(in_features, hidden, hps, num_envs, **kw)
@@ -214,6 +220,8 @@ class ConvLeagueDQN(ConvPopulationDQN):
     that a fetched weight serves them all).  Its Q is drl_convpop_act's bit
     for bit.  `train`, `member_net`, `save`, `params`, `counters` and
     `sample_slots` are the conv population's."""
+
+    _double_refusal = DOUBLE_LEAGUE_REFUSAL
 
     def __init__(self, obs_shape, conv_layers, dense_layers: Sequence[int], hps: Sequence[DQNHParams],
                  num_envs: int, **kw):
@@ -503,6 +511,8 @@ def parse_args(argv=None):
     except json.JSONDecodeError as e:
         raise ValueError(f"--grid is not valid JSON: {e}")
     points = expand_grid(grid)
+    from .train import refuse_double_dqn
+    refuse_double_dqn(args, "the league", points)
     if len(points) not in (1, own.learners):
         raise ValueError(f"--grid has {len(points)} points: one per learner ({own.learners}) or one shared point")
     args.learners = own.learners

@@ -81,6 +81,8 @@ def parse_args(argv=None):
     args.prioritized_replay = True
     check_per(args.per_alpha, args.per_beta, args.per_beta_steps, args.per_eps)
     points = expand_grid(grid)
+    from .train import refuse_double_dqn
+    refuse_double_dqn(args, "the prioritized population sweep (per_sweep)", points)
     for pt in points:
         check_per(*[pt.get(k, getattr(args, k)) for k in PER_OPTIONS])
     from .population import POP_MAX_MEMBERS

@@ -56,6 +56,7 @@ def _bind_pop(L):
         "drl_pop_replay_add": [D, i32, R, i64, i64, _vp, _vp, _vp, _vp, _vp, i32, _vp],
         "drl_pop_train": [D, i32, i32, _vp, R, i64, _vp],
         "drl_pop_sample_rows": [D, i32, i32, _vp, i64, _vp, _vp],
+        "drl_pop_double_train": [D, i32, i32, _vp, R, i64, _vp, _vp],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -139,6 +140,12 @@ class PopulationReplay:
                     dones=self.dones[s])
 
 
+DOUBLE_CONV_POP_REFUSAL = ("double_dqn: a conv population (ConvPopulationDQN) trains the max rule only; Double DQN "
+                           "is implemented for dense populations (PopulationDQN)")
+DOUBLE_PER_POP_REFUSAL = ("double_dqn: a prioritized population (PrioritizedPopulationDQN) trains the max rule only; "
+                          "Double DQN is implemented for uniform dense populations (PopulationDQN)")
+
+
 class PopulationDQN:
     """P dense DQN agents in one device allocation: member m's block is laid
     out as LargeBatchDQNLearner's / WideDQNLearner's (four parameter sets,
@@ -149,13 +156,22 @@ class PopulationDQN:
     defaults to the largest).  hidden: 1-3 widths, multiples of 8 up to 256.
     seeds: member m's initialisation seed (the online net from seeds[m], the
     target net from seeds[m] + 1, as `train` does); or `online` / `target`:
-    per member ([weights], [biases]) in torch layout."""
+    per member ([weights], [biases]) in torch layout.
+
+    A member whose hp.double_dqn is set trains with the Double DQN target
+    (drl_pop_double_train: the rule is a device byte per member, `double_mask`,
+    so both rules share one launch chain); with no such member `train` is
+    drl_pop_train."""
+
+    _double_refusal = None  # a subclass whose chain keeps the max rule: the message it refuses hp.double_dqn with
 
     def __init__(self, in_features: int, hidden: Sequence[int], hps: Sequence[DQNHParams], envs_per_member: int,
                  n_actions: int = NUM_ACTIONS, device=None, seeds: Optional[Sequence[int]] = None,
                  max_batch: Optional[int] = None, online=None, target=None, guard_bytes: int = 0):
         self.L = _bind_pop(_bind(lib()))
         self.hps = list(hps)
+        if self._double_refusal and any(hp.double_dqn for hp in self.hps):
+            raise ValueError(self._double_refusal)
         self.members = len(self.hps)
         self.E = int(envs_per_member)
         self.in_features, self.hidden, self.n_actions = int(in_features), tuple(int(w) for w in hidden), int(n_actions)
@@ -202,6 +218,10 @@ class PopulationDQN:
         self.epsilon = self._f32.as_strided((self.members,), (lay.member_stride // 4,),
                                             (lay.member.counters_off + 8) // 4)
         self._hp = (DrlDqnHParams * self.members)(*[hp.c() for hp in self.hps])
+        # the members' TD rule: a device byte each (nonzero: Double DQN), read by drl_pop_double_train's kernels
+        self.double_mask = torch.tensor([1 if hp.double_dqn else 0 for hp in self.hps], dtype=torch.uint8,
+                                        device=self.device)
+        self._any_double = any(hp.double_dqn for hp in self.hps)
         self.restart()
 
     # ---------------------------------------------------------------- state --
@@ -275,6 +295,12 @@ class PopulationDQN:
         member m trains iff replay.size >= its batch (decided on the device)."""
         if replay.obs.device != self.device or replay.members != self.members:
             raise ValueError("the replay must be on the population's device and hold one ring per member")
+        if self._any_double:
+            _check(self.L, self.L.drl_pop_double_train(ctypes.byref(self.desc), self.members, self.max_batch,
+                                                       _vp(self.block.data_ptr()), ctypes.byref(replay._c),
+                                                       replay.size, _vp(self.double_mask.data_ptr()),
+                                                       _stream(self.device)))
+            return
         _check(self.L, self.L.drl_pop_train(ctypes.byref(self.desc), self.members, self.max_batch,
                                             _vp(self.block.data_ptr()), ctypes.byref(replay._c), replay.size,
                                             _stream(self.device)))
@@ -366,12 +392,16 @@ class ConvPopulationDQN(PopulationDQN):
     `online` / `target`: per member ([weights], [biases]) in forward order
     (conv layers [out][in][k][k], then dense [out][in], the Q head last)."""
 
+    _double_refusal = DOUBLE_CONV_POP_REFUSAL
+
     def __init__(self, obs_shape, conv_layers, dense_layers: Sequence[int], hps: Sequence[DQNHParams],
                  envs_per_member: int, n_actions: int = NUM_ACTIONS, device=None,
                  seeds: Optional[Sequence[int]] = None, max_batch: Optional[int] = None, online=None, target=None,
                  guard_bytes: int = 0):
         self.L = _bind_convpop(_bind_pop(_bind(_bind_convnet(lib()))))
         self.hps = list(hps)
+        if any(hp.double_dqn for hp in self.hps):
+            raise ValueError(self._double_refusal)
         self.members = len(self.hps)
         self.E = int(envs_per_member)
         self.obs_shape = tuple(int(v) for v in obs_shape)
@@ -667,6 +697,8 @@ class PrioritizedPopulationDQN(PopulationDQN):
     slots -- PrioritizedDQNLearner's step bit for bit at the widths both take,
     whoever shares the population; stream-ordered, graph-capturable, a launch
     count that does not depend on the number of members."""
+
+    _double_refusal = DOUBLE_PER_POP_REFUSAL
 
     def __init__(self, *a, **kw):
         super().__init__(*a, **kw)

@@ -141,6 +141,10 @@ class SelfPlayReplay(PopulationReplay):
         self.size = min(self.size + M * E, self.capacity)
 
 
+DOUBLE_SELFPLAY_REFUSAL = ("double_dqn: self-play learners (SelfPlayDQN, ConvSelfPlayDQN) train the max rule only; "
+                           "Double DQN is implemented for single dense agents and dense populations")
+
+
 class SelfPlayDQN(LeagueDQN):
     """K learners over the same E envs, learner k on the drones
     `drones[k]` (K lists of M distinct drone indices; default k * M + j with
@@ -148,6 +152,8 @@ class SelfPlayDQN(LeagueDQN):
     weights on the code rows of each of its drones and writes those drones'
     columns of the action matrix (drl_selfplay_act).  `train`, `member_net`,
     `save`, `params`, `counters` and `sample_slots` are the population's."""
+
+    _double_refusal = DOUBLE_SELFPLAY_REFUSAL
 
     def __init__(self, in_features: int, hidden: Sequence[int], hps: Sequence[DQNHParams], num_envs: int,
                  drones=None, team: int = 1, **kw):
@@ -199,6 +205,8 @@ class ConvSelfPlayDQN(ConvLeagueDQN):
     M * E rows; Q is drl_convpop_act's bit for bit).  `train`, `member_net`,
     `save`, `params`, `counters` and `sample_slots` are the conv
     population's."""
+
+    _double_refusal = DOUBLE_SELFPLAY_REFUSAL
 
     def __init__(self, obs_shape, conv_layers, dense_layers: Sequence[int], hps: Sequence[DQNHParams],
                  num_envs: int, drones=None, team: int = 1, **kw):
@@ -460,6 +468,8 @@ def parse_args(argv=None):
     except json.JSONDecodeError as e:
         raise ValueError(f"--grid is not valid JSON: {e}")
     points = expand_grid(grid)
+    from .train import refuse_double_dqn
+    refuse_double_dqn(args, "self-play", points)
     if len(points) not in (1, own.learners):
         raise ValueError(f"--grid has {len(points)} points: one per learner ({own.learners}) or one shared point")
     args.learners, args.drones_per_learner, args.drones = own.learners, own.drones_per_learner, drones

@@ -25,7 +25,8 @@ from typing import List, Tuple
 
 # what a member may own (a DQNHParams field each): train's option -> why it can differ
 MEMBER_OPTIONS = ("batch_size", "learning_rate", "gamma", "tau", "target_update_interval", "epsilon_start",
-                  "epsilon_decay", "epsilon_decay_half_life_fraction", "epsilon_end", "epsilon_decay_every")
+                  "epsilon_decay", "epsilon_decay_half_life_fraction", "epsilon_end", "epsilon_decay_every",
+                  "double_dqn")  # (double_dqn: JSON booleans; the TD rule is chosen per member in one launch chain)
 # what the population shares, and why
 SHARED_OPTIONS = {
     "num_envs": "one env batch of members * num_envs envs serves the population: every member owns num_envs of them",
@@ -55,6 +56,8 @@ def expand_grid(grid: dict) -> List[dict]:
             raise ValueError(f"--grid: {k} is not a per-member option (one of {', '.join(MEMBER_OPTIONS)})")
         if not isinstance(v, list) or not v:
             raise ValueError(f"--grid: {k} must be a non-empty list")
+        if k == "double_dqn" and not all(isinstance(x, bool) for x in v):
+            raise ValueError("--grid: double_dqn takes JSON booleans (true / false)")
     keys = list(grid)
     return [dict(zip(keys, vals)) for vals in itertools.product(*[grid[k] for k in keys])]
 
@@ -133,6 +136,7 @@ def main(argv=None) -> dict:
         entry = {"member": m, **row, "batch_size": hp.batch, "learning_rate": hp.learning_rate, "gamma": hp.gamma,
                  "tau": hp.tau, "target_update_interval": hp.target_update_interval, "epsilon_end": hp.epsilon_end,
                  "epsilon_decay": hp.decay(), "epsilon_decay_every": hp.epsilon_decay_every,
+                 "double_dqn": bool(hp.double_dqn),
                  "eval_reward_mean": am, "eval_reward_std": asd, "final_epsilon": c["epsilon"],
                  "final_loss": c["loss"], "steps": c["step"], "train_steps": c["count"]}
         if args.save_final_checkpoint:

@@ -43,7 +43,7 @@ def train(params: EnvParams, num_envs: int, num_steps: int, hidden: Sequence[int
           reset_env_every: int = 100, memory_size: int = 100_000, seed: int = 0, env_offset: int = 0,
           action_seed: int = 2024, act_seed: int = 7, device=None, rank: int = 0, world: int = 1,
           group=None, network_type: str = "dense", conv_layers=None, conv_dense_layers: Sequence[int] = (),
-          per: Optional[dict] = None) -> TrainResult:
+          per: Optional[dict] = None, double_dqn: bool = False) -> TrainResult:
     """train_jax.py's training loop (see the module docstring).  hp: a
     dqn.DQNHParams (default: train_jax.py's defaults with num_steps, so
     epsilon decays as :133-134 schedules it).  hidden: 1-3 widths, each a
@@ -74,7 +74,14 @@ def train(params: EnvParams, num_envs: int, num_steps: int, hidden: Sequence[int
     ring is wrapped in a PrioritizedReplay and the learner is
     dqn.make_per_learner's at every batch (PrioritizedDQNLearner, or
     PrioritizedWideDQNLearner, or PrioritizedConvDQNLearner); one GPU only.
-    The returned `replay` is the wrapper."""
+    The returned `replay` is the wrapper.
+
+    double_dqn (--double_dqn): the learner's TD target is Double DQN's
+    (DQNHParams.double_dqn, set on `hp` here): dense nets of every width, on
+    the launch chain at every batch, uniform or prioritized; refused by name
+    for conv nets and for world > 1."""
+    import dataclasses
+
     from .dqn import (ConvQNetwork, DQNHParams, PrioritizedReplay, QNetwork, ReplayBuffer, WideQNetwork, is_wide,
                       make_learner, make_per_learner)
     from .distributed import shard_envs
@@ -91,6 +98,11 @@ def train(params: EnvParams, num_envs: int, num_steps: int, hidden: Sequence[int
         raise ValueError(WIDE_SHARDING_REFUSAL)
     if per is not None and world > 1:
         raise ValueError(PER_SHARDING_REFUSAL)
+    double_dqn = bool(double_dqn or (hp is not None and hp.double_dqn))
+    if double_dqn and network_type == "conv":
+        raise ValueError(DOUBLE_CONV_REFUSAL)
+    if double_dqn and world > 1:
+        raise ValueError(DOUBLE_SHARDING_REFUSAL)
     shard = shard_envs(num_envs, rank, world) if world > 1 else None
     env = BatchedDeliveryDrones(params, shard.num_envs if shard else num_envs, device=device,
                                 env_offset=shard.env_offset if shard else env_offset)
@@ -99,6 +111,8 @@ def train(params: EnvParams, num_envs: int, num_steps: int, hidden: Sequence[int
     r = params.window_radius
     D = (2 * r + 1) ** 2 * 6
     hp = hp or DQNHParams(num_steps=num_steps)
+    if double_dqn and not hp.double_dqn:
+        hp = dataclasses.replace(hp, double_dqn=True)
     if network_type == "conv":
         from .checkpoint import TRAIN_JAX_CONV_LAYERS
         W = 2 * r + 1
@@ -169,6 +183,10 @@ PER_WIDE_REFUSAL = ("--prioritized_replay with --hidden_layers wider than 128 is
                     "trains dense nets of widths up to 128 only")
 PER_SHARDING_REFUSAL = ("--prioritized_replay with --use_sharding is not implemented: the priority tree covers one "
                         "GPU's ring")
+DOUBLE_CONV_REFUSAL = ("--double_dqn with --network_type conv is not implemented: Double DQN trains dense nets "
+                       "(the conv chains keep the max rule)")
+DOUBLE_SHARDING_REFUSAL = ("--double_dqn with --use_sharding is not implemented: the global (sharded) learner keeps "
+                           "the max rule")
 WIDE_SHARDING_REFUSAL = ("--use_sharding with --hidden_layers wider than 128 is not implemented: the global "
                          "(sharded) learner trains dense nets of widths up to 128 only")
 
@@ -255,6 +273,8 @@ def parse_args(argv=None):
     ap.add_argument("--per_beta_steps", type=int, default=None,
                     help="learner steps over which beta anneals to 1 (default: num_steps; 0: per_beta throughout)")
     ap.add_argument("--per_eps", type=float, default=1e-6)
+    ap.add_argument("--double_dqn", action="store_true", default=False,
+                    help="Double DQN targets: the target net's value at the online net's argmax on next_obs")
     args = ap.parse_args(argv)
     # train_jax.py:393-402's validations
     if args.num_envs <= 0:
@@ -267,6 +287,10 @@ def parse_args(argv=None):
         raise ValueError(CONV_SHARDING_REFUSAL)
     if args.use_sharding and args.network_type == "dense" and max(args.hidden_layers) > 128:
         raise ValueError(WIDE_SHARDING_REFUSAL)
+    if args.double_dqn and args.network_type == "conv":
+        raise ValueError(DOUBLE_CONV_REFUSAL)
+    if args.double_dqn and args.use_sharding:
+        raise ValueError(DOUBLE_SHARDING_REFUSAL)
     if args.per_beta_steps is None:
         args.per_beta_steps = args.num_steps  # (the usual anneal to 1 over the run)
     if args.prioritized_replay:
@@ -293,6 +317,14 @@ def refuse_prioritized(args, driver: str):
     if getattr(args, "prioritized_replay", False):
         raise ValueError(f"--prioritized_replay is not implemented for {driver}: it trains one dense agent "
                          "(python -m dronerl_amd.train)")
+
+
+def refuse_double_dqn(args, driver: str, points=()):
+    """The drivers whose learners keep the max rule refuse --double_dqn by
+    name, on the command line and as a --grid key (`points`)."""
+    if getattr(args, "double_dqn", False) or any("double_dqn" in pt for pt in points):
+        raise ValueError(f"--double_dqn is not implemented for {driver}: Double DQN trains dense single agents "
+                         "(python -m dronerl_amd.train, per_train) and dense populations (python -m dronerl_amd.sweep)")
 
 
 def _parse_conv_layers(value: str):
@@ -331,7 +363,7 @@ def hparams_of(args):
                       target_update_interval=args.target_update_interval, epsilon_start=args.epsilon_start,
                       epsilon_decay=decay, epsilon_end=args.epsilon_end,
                       epsilon_decay_every=args.epsilon_decay_every, num_steps=args.num_steps,
-                      sample_seed=args.seed)
+                      sample_seed=args.seed, double_dqn=bool(getattr(args, "double_dqn", False)))
 
 
 def main(argv=None) -> dict:

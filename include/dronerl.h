@@ -1060,6 +1060,64 @@ int drl_pop_sample_rows(const drl_widenet_desc* d, int32_t members, int32_t max_
                         int64_t* d_slots, hipStream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Double DQN targets (van Hasselt et al. 2016) for the dense learners' launch
+ * chains: an option beside the max rule, which stays the default of every
+ * other call.  One step is the learner block of the corresponding max-rule
+ * call (drl_dqn_large_train and the calls built on it) with one change in the
+ * TD rule.  For sampled row b with A actions, all f32:
+ *
+ *   q  = Q_online(obs_b)        (as in the max-rule call)
+ *   qs = Q_online(next_obs_b)   the online parameters the step started with,
+ *                               in the chain's dot-product order (four partial
+ *                               sums over k mod 4, (s0+s1)+(s2+s3), + bias; no
+ *                               FMA contraction)
+ *   qt = Q_target(next_obs_b)   (as in the max-rule call)
+ *   a* = 0; for j = 1 .. A-1: if qs[j] > qs[a*]: a* = j
+ *                               (jnp.argmax: the first maximum; a NaN never wins)
+ *   td = r + (gamma * qt[a*]) * (1 - done)
+ *   d  = q[a] - td
+ *
+ * Everything behind d is the max-rule call's: the squared error, the Q head's
+ * delta (d + d) / B, the backward pass, Adam, the target blend, the counters
+ * and the re-pack; a prioritized step puts the row's weight where it lies
+ * there and keeps |d|.  No gradient flows through qs: the selection is an
+ * index.  So (1) with the target set equal to the online set when a step
+ * starts, a Double step is the max-rule step bit for bit; (2) ties resolve to
+ * the lowest index; (3) the row draw, the counters, the epsilon schedule and
+ * the packed image are the max-rule call's.
+ *
+ * The agent blocks, layouts, init calls, *_sample_rows, hyperparameter structs
+ * and records are the max-rule calls' own.  The selector's forward rides in
+ * the forward launches as a third grid slice and keeps its activations in the
+ * scratch's delta words, so a Double step has the launches, the scratch and
+ * the plan of the max-rule step.  Every argument is validated before any
+ * device work with the max-rule call's checks and messages; kernel nodes
+ * only, one stream, nothing allocated, nothing synchronises: graph-capturable.
+ * ------------------------------------------------------------------------ */
+/* drl_dqn_large_train (its arguments) with the TD rule above. */
+int drl_dqn_double_train(const drl_qnet_desc* d, const drl_dqn_hparams* h, void* d_agent, void* d_packed,
+                         const struct drl_replay* r, int64_t size, hipStream_t stream);
+/* drl_widenet_dqn_train (its arguments) with the TD rule above. */
+int drl_widenet_dqn_double_train(const drl_widenet_desc* d, const drl_dqn_hparams* h, void* d_agent, void* d_packed,
+                                 const struct drl_replay* r, int64_t size, hipStream_t stream);
+/* drl_dqn_per_train (its arguments) with the TD rule above: the row's weight
+ * on w * (d * d) and w * ((d + d) / batch), |d| to the block's absd. */
+int drl_dqn_double_per_train(const drl_qnet_desc* d, const drl_dqn_hparams* h, const drl_per_hparams* ph,
+                             void* d_agent, void* d_packed, const struct drl_replay* r, int64_t size, void* d_per,
+                             hipStream_t stream);
+/* drl_widenet_dqn_per_train (its arguments) with the TD rule above. */
+int drl_widenet_dqn_double_per_train(const drl_widenet_desc* d, const drl_dqn_hparams* h, const drl_per_hparams* ph,
+                                     void* d_agent, void* d_packed, const struct drl_replay* r, int64_t size,
+                                     void* d_per, hipStream_t stream);
+/* drl_pop_train with the rule chosen per member: d_double is a DEVICE array of
+ * `members` bytes, nonzero = member m's TD rule is the one above, 0 = the max
+ * rule (the member's selector slice returns at once).  With every byte 0 the
+ * population block is left byte for byte as drl_pop_train leaves it. */
+int drl_pop_double_train(const drl_widenet_desc* d, int32_t members, int32_t max_batch, void* d_pop,
+                         const drl_replay* r, int64_t size, const uint8_t* d_double /* DEVICE [members] */,
+                         hipStream_t stream);
+
+/* ------------------------------------------------------------------------
  * Prioritized replay for a population of dense DQN agents: every member
  * owns a priority tree over its ring and its own drl_per_hparams (alpha,
  * beta0, beta_steps, eps), so one population sweeps them.  The members
