@@ -45,6 +45,7 @@ SOURCES = [os.path.join(CSRC, "dronerl_kernels.hip"), os.path.join(CSRC, "droner
            os.path.join(CSRC, "doubledqn", "dronerl_doubledqn_api.cpp")]
 DEPS = SOURCES + [os.path.join(CSRC, "dronerl_internal.h"), os.path.join(CSRC, "dronerl_act_common.h"),
                   os.path.join(CSRC, "dronerl_learn_common.h"), os.path.join(CSRC, "dronerl_learn_args.h"),
+                  os.path.join(CSRC, "dronerl_learn_front.h"), os.path.join(CSRC, "dronerl_host.h"),
                   os.path.join(CSRC, "convlearn", "dronerl_convlearn_layout.h"),
                   os.path.join(CSRC, "convlearn", "dronerl_convlearn_rows.h"),
                   os.path.join(CSRC, "convlarge", "dronerl_convlarge_layout.h"),

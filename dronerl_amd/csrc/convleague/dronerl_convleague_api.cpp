@@ -7,22 +7,12 @@
 #include <string.h>
 
 #include "../../../include/dronerl.h"
+#include "../dronerl_host.h"
 #include "../dronerl_internal.h"
 #include "dronerl_convleague_layout.h"
 
-extern "C" __attribute__((visibility("hidden"))) int drl_internal_fail(const char* msg);
-
-namespace {
-
-int fail(const char* m) { return drl_internal_fail(m); }
-
-int hip_fail(int e, const char* what) {
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString((hipError_t)e));
-    return fail(buf);
-}
-
-}  // namespace
+using drl::fail;
+using drl::hip_fail;
 
 extern "C" {
 

@@ -9,19 +9,13 @@
 #include <vector>
 
 #include "../../../include/dronerl.h"
+#include "../dronerl_host.h"
 #include "dronerl_convnet_layout.h"
 
-extern "C" __attribute__((visibility("hidden"))) int drl_internal_fail(const char* msg);
+using drl::fail;
+using drl::hip_fail;
 
 namespace {
-
-int fail(const char* m) { return drl_internal_fail(m); }
-
-int hip_fail(int e, const char* what) {
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString((hipError_t)e));
-    return fail(buf);
-}
 
 // Every limit is checked here, by every call: nothing is refused at launch.
 int cv_layout(const drl_convnet_desc* d, drl::cv::Layout* L) {

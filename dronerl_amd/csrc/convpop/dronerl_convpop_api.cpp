@@ -10,20 +10,15 @@
 #include <vector>
 
 #include "../../../include/dronerl.h"
+#include "../dronerl_host.h"
 #include "../dronerl_internal.h"
+#include "../dronerl_learn_args.h"
 #include "dronerl_convpop_layout.h"
 
-extern "C" __attribute__((visibility("hidden"))) int drl_internal_fail(const char* msg);
+using drl::fail;
+using drl::hip_fail;
 
 namespace {
-
-int fail(const char* m) { return drl_internal_fail(m); }
-
-int hip_fail(int e, const char* what) {
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString((hipError_t)e));
-    return fail(buf);
-}
 
 // Every limit is checked here, by every call: nothing is refused at launch.
 int cp_plan(const drl_convnet_desc* d, int32_t members, int32_t max_batch, drl::cp::Plan* P) {
@@ -38,8 +33,7 @@ int check_block(const void* d_pop) {
 
 // the rings of a population: drl_replay's arrays, [members][capacity] each
 int check_rings(const drl::cp::Plan& P, const drl_replay* r) {
-    if (!r || !r->obs || !r->next_obs || !r->actions || !r->rewards || !r->dones) return fail("replay buffers are NULL");
-    if (r->capacity < 1 || r->capacity >= ((int64_t)1 << 31)) return fail("replay capacity must be in [1, 2^31)");
+    if (const char* msg = drl::check_ring(r)) return fail(msg);
     if ((int64_t)r->obs_floats * 4 != drl::lay::code_bytes(P.code_w))
         return fail("a population's replay rows are policy codes (obs_floats = drl_policy_code_bytes / 4 words)");
     if ((uintptr_t)r->obs % 4 || (uintptr_t)r->next_obs % 4 || (uintptr_t)r->actions % 4 || (uintptr_t)r->rewards % 4)
@@ -87,10 +81,7 @@ int drl_convpop_init(const drl_convnet_desc* d, int32_t members, int32_t max_bat
     for (int m = 0; m < members; ++m) {
         const char* what = nullptr;
         if (h[m].batch < 1 || h[m].batch > max_batch) what = "batch must be in [1, max_batch]";
-        else if (h[m].target_update_interval < 1 || h[m].epsilon_decay_every < 1)
-            what = "target_update_interval and epsilon_decay_every must be >= 1";
-        else if (!(h[m].beta1 >= 0.0 && h[m].beta1 < 1.0 && h[m].beta2 >= 0.0 && h[m].beta2 < 1.0))
-            what = "beta1 and beta2 must be in [0, 1)";
+        else what = drl::check_hparam_ranges(&h[m]);
         if (what) {
             snprintf(buf, sizeof buf, "member %d: %s", m, what);
             return fail(buf);

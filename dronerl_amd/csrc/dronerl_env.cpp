@@ -11,6 +11,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include "dronerl_host.h"
 #include "dronerl_internal.h"
 
 struct drl_env {
@@ -26,9 +27,6 @@ struct drl_env {
     int32_t* err;
 };
 
-// error text shared with dronerl_api.cpp
-extern "C" __attribute__((visibility("hidden"))) int drl_internal_fail(const char* msg);
-
 namespace {
 
 // Runs `f` with env->device current, restoring the caller's device after.
@@ -43,12 +41,7 @@ int on_device(const drl_env* env, F f) {
     return rc;
 }
 
-int hip_check(hipError_t e, const char* what) {
-    if (e == hipSuccess) return 0;
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-    return drl_internal_fail(buf);
-}
+int hip_check(hipError_t e, const char* what) { return e == hipSuccess ? 0 : drl::hip_fail(e, what); }
 
 void free_env(drl_env* env) {
     if (!env) return;

@@ -11,15 +11,16 @@
 #include <vector>
 
 #include "../../include/dronerl.h"
+#include "dronerl_host.h"
 #include "dronerl_internal.h"
+#include "dronerl_learn_args.h"
 
-extern "C" __attribute__((visibility("hidden"))) int drl_internal_fail(const char* msg);
+using drl::fail;
+using drl::hip_fail;
 
 namespace {
 
 constexpr int kQnetLdsMax = 160 * 1024;
-
-int fail(const char* m) { return drl_internal_fail(m); }
 
 // Validate a description and lay the packed net out (see QnetLayout).
 int qnet_layout(const drl_qnet_desc* d, drl::QnetLayout* L) {
@@ -112,12 +113,6 @@ int qnet_layout(const drl_qnet_desc* d, drl::QnetLayout* L) {
     L->total_vec += 1;
     if (L->lds_vec * 16 > kQnetLdsMax) return fail("the packed network does not fit the 160 KB LDS of a CU");
     return 0;
-}
-
-int hip_fail(hipError_t e, const char* what) {
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-    return fail(buf);
 }
 
 int num_cus() {
@@ -538,7 +533,7 @@ int drl_dqn_init(const drl_qnet_desc* d, int32_t batch, void* d_agent, float eps
     if (qnet_layout(d, &L)) return -1;
     DqnPlan P;
     if (dqn_plan(d, batch, L, &P)) return -1;
-    if (!d_agent || (uintptr_t)d_agent % 16) return fail("the agent block must be a 16-byte aligned device pointer");
+    if (const char* msg = drl::check_agent_block(d_agent)) return fail(msg);
     uint8_t* base = static_cast<uint8_t*>(d_agent);
     const size_t set = (size_t)P.pub.n_params * 4;
     if (hipError_t e = hipMemsetAsync(base + P.pub.m_off, 0, 2 * set, stream); e != hipSuccess)
@@ -573,22 +568,12 @@ static int dqn_train_impl(const drl_qnet_desc* d, const drl_dqn_hparams* h, void
     if (!h) return fail("hparams is NULL");
     DqnPlan P;
     if (dqn_plan(d, h->batch, L, &P)) return -1;
-    if (h->target_update_interval < 1 || h->epsilon_decay_every < 1)
-        return fail("target_update_interval and epsilon_decay_every must be >= 1");
-    if (!(h->beta1 >= 0.0 && h->beta1 < 1.0 && h->beta2 >= 0.0 && h->beta2 < 1.0))
-        return fail("beta1 and beta2 must be in [0, 1)");
-    if (!d_agent || (uintptr_t)d_agent % 16) return fail("the agent block must be a 16-byte aligned device pointer");
-    if (!d_packed || (uintptr_t)d_packed % 16) return fail("packed buffer must be a 16-byte aligned device pointer");
-    if (!r || !r->obs || !r->next_obs || !r->actions || !r->rewards || !r->dones) return fail("replay buffers are NULL");
-    if (r->capacity < 1 || r->capacity >= ((int64_t)1 << 31)) return fail("replay capacity must be in [1, 2^31)");
-    if (size < 0 || size > r->capacity) return fail("size must be in [0, capacity]");
-    if (L.code_w) {
-        if ((int64_t)r->obs_floats * 4 != drl::lay::code_bytes(L.code_w))
-            return fail("a DRL_QNET_INPUT_CODE net's replay rows are policy codes (drl_policy_code_bytes / 4 words)");
-    } else if (r->obs_floats < d->in_features) {
-        return fail("replay obs_floats < in_features");
-    }
-    if ((uintptr_t)r->obs % 4 || (uintptr_t)r->next_obs % 4) return fail("replay rows must be 4-byte aligned");
+    // the chain learners' checks in their order (dronerl_learn_args.h); the argument block below is this
+    // learner's own
+    if (const char* msg = drl::check_learn_call(h, d_agent, d_packed, r, drl::RingCapacity::kCheckedHere))
+        return fail(msg);
+    if (const char* msg = drl::check_learn_size(r, size)) return fail(msg);
+    if (const char* msg = drl::check_learn_rows(r, L.code_w, d->in_features, drl::kShortRowsDense)) return fail(msg);
     if (size >= h->batch) {  // the workgroups poll each other's hand-offs: all of them must fit at once
         const int cap = dqn_resident_capacity(P.lds);
         if (cap < 0) return fail("drl_dqn_train: the occupancy query failed");
@@ -767,7 +752,7 @@ int drl_dqn_sample_rows(const drl_qnet_desc* d, const drl_dqn_hparams* h, const 
     if (!h) return fail("hparams is NULL");
     DqnPlan P;
     if (dqn_plan(d, h->batch, L, &P)) return -1;
-    if (!d_agent || (uintptr_t)d_agent % 16) return fail("the agent block must be a 16-byte aligned device pointer");
+    if (const char* msg = drl::check_agent_block(d_agent)) return fail(msg);
     if (!d_slots || (uintptr_t)d_slots % 8) return fail("d_slots must be an 8-byte aligned device pointer");
     if (size < 1) return fail("size must be >= 1 (buffers.py can_sample: nothing is drawn from an empty ring)");
     hipError_t e = drl::launch_dqn_sample(static_cast<const uint8_t*>(d_agent) + P.pub.counters_off, h->sample_seed,
@@ -783,8 +768,8 @@ int drl_dqn_train_fresh(const drl_qnet_desc* d, const drl_dqn_hparams* h, void* 
 
 }  // extern "C"
 
-// The description check and the pack launch's arguments for the other dense learner's host API
-// (largelearn/dronerl_largelearn_api.cpp): one rule for what a drl_qnet_desc may hold, one packed layout.
+// The description check and the pack launch's arguments for the chain learners' dense family
+// (dronerl_learn_front.h): one rule for what a drl_qnet_desc may hold, one packed layout.
 namespace drl {
 int qnet_layout_of(const drl_qnet_desc* d, QnetLayout* L) { return qnet_layout(d, L); }
 void qnet_pack_args(const QnetLayout& L, void* d_packed, const float* const* w, const float* const* b, QnetPack* p) {

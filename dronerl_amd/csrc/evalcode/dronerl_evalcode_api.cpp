@@ -7,21 +7,11 @@
 #include <string.h>
 
 #include "../../../include/dronerl.h"
+#include "../dronerl_host.h"
 #include "dronerl_evalcode_layout.h"
 
-extern "C" __attribute__((visibility("hidden"))) int drl_internal_fail(const char* msg);
-
-namespace {
-
-int fail(const char* m) { return drl_internal_fail(m); }
-
-int hip_fail(hipError_t e, const char* what) {
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-    return fail(buf);
-}
-
-}  // namespace
+using drl::fail;
+using drl::hip_fail;
 
 extern "C" {
 

@@ -173,12 +173,6 @@ void launch_large_backward_update(const LearnArgs& a, hipStream_t s);
 void launch_large_blend(const LearnArgs& a, hipStream_t s);
 void launch_large_counters(const LearnArgs& a, hipStream_t s);
 int launch_large_sample(const void* counters, uint64_t seed, int batch, int64_t size, int64_t* out, hipStream_t s);
-// (host, dronerl_largelearn_api.cpp) drl_dqn_large_train's checks behind its plan (a.P), then everything of the
-// argument block but pack_status: 0, or -1 with the message for drl_last_error set.  in_features: the net's, for
-// f32 rows.  The calls that run this chain with kernels of their own (doubledqn/) take it as it is.
-__attribute__((visibility("hidden"))) int large_train_args(LearnArgs& a, int in_features, const drl_dqn_hparams* h,
-                                                           void* d_agent, void* d_packed, const drl_replay* r,
-                                                           int64_t size);
 
 }  // namespace ll
 }  // namespace drl

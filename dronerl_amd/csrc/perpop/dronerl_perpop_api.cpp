@@ -9,23 +9,17 @@
 #include <vector>
 
 #include "../../../include/dronerl.h"
+#include "../dronerl_host.h"
 #include "../dronerl_internal.h"
 #include "dronerl_perpop_layout.h"
 
-extern "C" __attribute__((visibility("hidden"))) int drl_internal_fail(const char* msg);
+using drl::fail;
+using drl::hip_fail;
 
 namespace {
 
 using drl::perpop::ChainArgs;
 using drl::perpop::TreeSetArgs;
-
-int fail(const char* m) { return drl_internal_fail(m); }
-
-int hip_fail(int e, const char* what) {
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString((hipError_t)e));
-    return fail(buf);
-}
 
 // Every limit is checked here, by every call: nothing is refused at launch.
 int pper_plan(int32_t members, int64_t capacity, int32_t max_batch, drl::perpop::Plan* P) {

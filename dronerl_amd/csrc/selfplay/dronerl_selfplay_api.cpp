@@ -7,20 +7,15 @@
 #include <string.h>
 
 #include "../../../include/dronerl.h"
+#include "../dronerl_host.h"
 #include "../dronerl_internal.h"
+#include "../dronerl_learn_args.h"
 #include "dronerl_selfplay_layout.h"
 
-extern "C" __attribute__((visibility("hidden"))) int drl_internal_fail(const char* msg);
+using drl::fail;
+using drl::hip_fail;
 
 namespace {
-
-int fail(const char* m) { return drl_internal_fail(m); }
-
-int hip_fail(int e, const char* what) {
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString((hipError_t)e));
-    return fail(buf);
-}
 
 // The description, the learners, their teams and the drones: every limit is checked here, by both calls.
 int selfplay_plan(const drl_widenet_desc* d, int32_t members, int32_t max_batch, const int32_t* drones, int32_t team,
@@ -98,8 +93,7 @@ int drl_selfplay_replay_add(const drl_widenet_desc* d, int32_t members, const dr
                             const uint8_t* d_dones, int32_t n_drones, hipStream_t stream) {
     drl::pop::Plan P;
     if (selfplay_plan(d, members, 1, drones, team, n_drones, &P)) return -1;
-    if (!r || !r->obs || !r->next_obs || !r->actions || !r->rewards || !r->dones) return fail("replay buffers are NULL");
-    if (r->capacity < 1 || r->capacity >= ((int64_t)1 << 31)) return fail("replay capacity must be in [1, 2^31)");
+    if (const char* msg = drl::check_ring(r)) return fail(msg);
     if ((int64_t)r->obs_floats * 4 != drl::lay::code_bytes(P.P.code_w))
         return fail("self-play replay rows are policy codes (obs_floats = drl_policy_code_bytes / 4 words)");
     if ((uintptr_t)r->obs % 4 || (uintptr_t)r->next_obs % 4 || (uintptr_t)r->actions % 4 || (uintptr_t)r->rewards % 4)

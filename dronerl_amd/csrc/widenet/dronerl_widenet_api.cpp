@@ -1,6 +1,7 @@
 // dronerl_widenet_api.cpp — C ABI of the wide dense Q-networks (include/dronerl.h drl_widenet_*; kernels in
-// dronerl_widenet.hip, layout in dronerl_widenet_layout.h).  The learner calls run the large-batch learner's
-// launch chain (largelearn/) on a plan with this family's width limit, then the wide pack kernel.
+// dronerl_widenet.hip, layout in dronerl_widenet_layout.h).  The learner calls are the shared front end's
+// (../dronerl_learn_front.h) on the wide family: the large-batch learner's launch chain (largelearn/) on a plan
+// with this family's width limit, then the wide pack kernel.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -11,37 +12,18 @@
 
 #include "../../../include/dronerl.h"
 #include "../dronerl_internal.h"
-#include "../dronerl_learn_args.h"
-#include "../largelearn/dronerl_largelearn_layout.h"
+#include "../dronerl_learn_front.h"
 #include "dronerl_widenet_layout.h"
 
-extern "C" __attribute__((visibility("hidden"))) int drl_internal_fail(const char* msg);
+namespace front = drl::front;
+using drl::fail;
+using drl::hip_fail;
 
 namespace {
-
-int fail(const char* m) { return drl_internal_fail(m); }
-
-int hip_fail(int e, const char* what) {
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString((hipError_t)e));
-    return fail(buf);
-}
 
 // Every limit is checked here, by every call: nothing is refused at launch.
 int wn_layout(const drl_widenet_desc* d, drl::wn::Layout* L) {
     const char* msg = drl::wn::layout(d, L);
-    return msg ? fail(msg) : 0;
-}
-
-// ... and the learner's plan for that net at `batch`
-int wn_plan(const drl_widenet_desc* d, int32_t batch, drl::wn::Layout* L, drl::ll::Plan* P) {
-    if (wn_layout(d, L)) return -1;
-    int32_t in[drl::wn::kMaxLayers], out[drl::wn::kMaxLayers];
-    for (int l = 0; l < L->n_layers; ++l) {
-        in[l] = L->l[l].in;
-        out[l] = L->l[l].out;
-    }
-    const char* msg = drl::ll::plan(L->n_layers, in, out, L->code_w, batch, P, drl::wn::kMaxWidth);
     return msg ? fail(msg) : 0;
 }
 
@@ -130,76 +112,24 @@ int drl_widenet_act(const drl_widenet_desc* d, const void* d_packed, const void*
 }
 
 int drl_widenet_dqn_layout_query(const drl_widenet_desc* d, int32_t batch, drl_dqn_layout* layout) {
-    drl::wn::Layout L;
-    drl::ll::Plan P;
-    if (wn_plan(d, batch, &L, &P)) return -1;
-    if (!layout) return fail("layout is NULL");
-    *layout = P.pub;
-    return 0;
+    return front::layout_query<front::Wide>(d, batch, layout);
 }
 
 int drl_widenet_dqn_init(const drl_widenet_desc* d, int32_t batch, void* d_agent, float epsilon_start,
                          hipStream_t stream) {
-    drl::wn::Layout L;
-    drl::ll::Plan P;
-    if (wn_plan(d, batch, &L, &P)) return -1;
-    if (!d_agent || (uintptr_t)d_agent % 16) return fail("the agent block must be a 16-byte aligned device pointer");
-    uint8_t* base = static_cast<uint8_t*>(d_agent);
-    // the moments; the init kernel sets the counters.  The scratch needs no clearing (drl_dqn_large_init).
-    if (hipError_t e = hipMemsetAsync(base + P.pub.m_off, 0, (size_t)(P.pub.counters_off - P.pub.m_off), stream);
-        e != hipSuccess)
-        return hip_fail((int)e, "drl_widenet_dqn_init moments");
-    hipError_t e = drl::launch_dqn_init(base + P.pub.counters_off, epsilon_start, stream);
-    return e == hipSuccess ? 0 : hip_fail((int)e, "drl_widenet_dqn_init launch");
+    return front::init<front::Wide>("drl_widenet_dqn_init", d, batch, d_agent, epsilon_start, stream);
 }
 
 int drl_widenet_dqn_train(const drl_widenet_desc* d, const drl_dqn_hparams* h, void* d_agent, void* d_packed,
                           const drl_replay* r, int64_t size, hipStream_t stream) {
-    drl::wn::PackArgs pk;
-    memset(&pk, 0, sizeof pk);
-    drl::ll::LearnArgs a;
-    memset(&a, 0, sizeof a);
-    if (!h) {
-        if (wn_plan(d, 1, &pk.L, &a.P)) return -1;
-        return fail("hparams is NULL");
-    }
-    if (wn_plan(d, h->batch, &pk.L, &a.P)) return -1;
-    const drl::ll::Plan& P = a.P;
-    if (const char* msg = drl::check_learn_call(h, d_agent, d_packed, r)) return fail(msg);
-    if (r->capacity < 1 || r->capacity >= ((int64_t)1 << 31)) return fail("replay capacity must be in [1, 2^31)");
-    if (size < 0 || size > r->capacity) return fail("size must be in [0, capacity]");
-    if (const char* msg = drl::check_learn_rows(r, P.code_w, d->in_features, "replay obs_floats < in_features"))
-        return fail(msg);
-    drl::fill_learn_args(a, P.pub, P.code_w, h, d_agent, r, size);
-    // the act's image of the new online set: the wide pack kernel on the online set, so the image is a fresh
-    // drl_widenet_pack's byte for byte; the counters kernel clears the status vector (kernel nodes only)
-    for (int l = 0; l < P.n_layers; ++l) {
-        pk.w[l] = a.online + P.woff[l];
-        pk.b[l] = a.online + P.boff[l];
-    }
-    pk.packed = static_cast<uint32_t*>(d_packed);
-    a.pack_status = pk.packed + pk.L.status;
-    if (const int e = drl::ll::launch_large_train(a, stream); e != 0)
-        return hip_fail(e, "drl_widenet_dqn_train launch");
-    const int e = drl::wn::launch_widenet_pack(pk, stream);
-    return e == 0 ? 0 : hip_fail(e, "drl_widenet_dqn_train pack launch");
+    return front::train<front::Wide, drl::ll::LearnArgs, front::NullHparams::kPlanAtBatch1>(
+        "drl_widenet_dqn_train", d, h, nullptr, d_agent, d_packed, r, size, nullptr, stream,
+        front::uniform<drl::ll::LearnArgs, drl::ll::launch_large_train>);
 }
 
 int drl_widenet_dqn_sample_rows(const drl_widenet_desc* d, const drl_dqn_hparams* h, const void* d_agent,
                                 int64_t size, int64_t* d_slots, hipStream_t stream) {
-    drl::wn::Layout L;
-    drl::ll::Plan P;
-    if (!h) {
-        if (wn_plan(d, 1, &L, &P)) return -1;
-        return fail("hparams is NULL");
-    }
-    if (wn_plan(d, h->batch, &L, &P)) return -1;
-    if (!d_agent || (uintptr_t)d_agent % 16) return fail("the agent block must be a 16-byte aligned device pointer");
-    if (!d_slots || (uintptr_t)d_slots % 8) return fail("d_slots must be an 8-byte aligned device pointer");
-    if (size < 1) return fail("size must be >= 1 (buffers.py can_sample: nothing is drawn from an empty ring)");
-    const int e = drl::ll::launch_large_sample(static_cast<const uint8_t*>(d_agent) + P.pub.counters_off, h->sample_seed,
-                                               h->batch, size, d_slots, stream);
-    return e == 0 ? 0 : hip_fail(e, "drl_widenet_dqn_sample_rows launch");
+    return front::sample_rows<front::Wide>("drl_widenet_dqn_sample_rows", d, h, d_agent, size, d_slots, stream);
 }
 
 }  // extern "C"

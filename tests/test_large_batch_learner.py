@@ -173,6 +173,26 @@ def test_largelearn_layout_places_every_scratch_word_once(tmp_path):
     assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout + r.stderr
 
 
+def test_learn_args_checks_and_fill_on_host_structs(tmp_path):
+    """tests/native/learn_args_check.cpp, a stand-alone program under the
+    address and undefined-behaviour sanitizers: what every chain learner's
+    train call shares behind its plan (csrc/dronerl_learn_args.h and
+    per/dronerl_per_learn_args.h), for a dense net at batches 1 and 4096, the
+    wide family's 256-wide limit and conv nets at both conv plans, uniform
+    and prioritized: each fault of one list is refused with its text, a
+    refused call writes nothing, and a good call puts every pointer at the
+    fake base + the public layout's offset.  Nothing is loaded into Python."""
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not available")
+    exe = str(tmp_path / "learn_args_check")
+    san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined"]
+    subprocess.run([hipcc, "-O1", "-g", "-std=c++17", *san, "-I", os.path.join(REPO, "include"), "-o", exe,
+                    os.path.join(HERE, "native", "learn_args_check.cpp")], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout + r.stderr
+
+
 # Every __global__ kernel under csrc/largelearn/ and the -m gpu test that launches it.
 KERNEL_TESTS = {
     "drl_dqn_large_rows_kernel": "test_large_batch_learner.py::test_large_learner_matches_oracle_bit_exact",

@@ -579,19 +579,10 @@ SIZE_BOUNDS = {
      "inline int32_t fastdiv_magic(int d) { return d > 1 ? (int32_t)(uint32_t)((((uint64_t)1 << 32) + d - 1) / d) : 0; }"):
         _MAGIC,
 }
-_CAP_LINE = 'if (r->capacity < 1 || r->capacity >= ((int64_t)1 << 31)) return fail("replay capacity must be in [1, 2^31)");'
-for _f in ("dronerl_qnet_api.cpp", "widenet/dronerl_widenet_api.cpp", "convlearn/dronerl_convlearn_api.cpp",
-           "convlarge/dronerl_convlarge_api.cpp"):
-    SIZE_BOUNDS[(_f, _CAP_LINE)] = ("-- a capacity check on an int32 field (the learner's replay slot index), a host "
-                                    "refusal before any device work; no launch picks a path from it")
-for _f, _t in {
-    "largelearn/dronerl_largelearn_api.cpp": "test_large_batch_learner.py::test_large_calls_validate_before_device_work",
-    "convpop/dronerl_convpop_api.cpp": "test_conv_population.py::test_convpop_calls_validate_before_device_work",
-    "population/dronerl_population_api.cpp": "test_population.py::test_population_calls_validate_before_device_work",
-    "league/dronerl_league_api.cpp": "test_league.py::test_league_calls_validate_before_device_work",
-    "selfplay/dronerl_selfplay_api.cpp": "test_selfplay.py::test_selfplay_calls_validate_before_device_work",
-}.items():
-    SIZE_BOUNDS[(_f, _CAP_LINE)] = "-- " + _CAP + _t
+# the one capacity refusal of every learner, population, league and self-play call (check_ring)
+SIZE_BOUNDS[("dronerl_learn_args.h",
+             'if (r->capacity < 1 || r->capacity >= ((int64_t)1 << 31)) return "replay capacity must be in [1, 2^31)";')] = (
+    "-- " + _CAP + "test_large_batch_learner.py::test_large_calls_validate_before_device_work")
 _ENVS_LINE = "if (num_envs < 1 || num_envs * n_drones >= ((int64_t)1 << 31))"
 for _f, _t in {
     "league/dronerl_league_api.cpp": "test_league.py::test_league_calls_validate_before_device_work",
